@@ -11,9 +11,16 @@ gives the Q5 count.
 One step = one watermark batch: (multi-GPU: partition by key group -> RCCL all-to-all) ->
 gw_ingest_device -> gw_advance_watermark (fires every 10th step) -> fired rows consumed
 (discarded, like the reference's DiscardingSink).  Inputs are pre-generated in HBM before
-the timed region.  N GPUs = N processes, key groups sharded by
+the timed region; a run of more steps than HBM should hold (STRETCH_EVENTS) generates them a
+stretch of whole fire cycles at a time and stops the clock in between.  N GPUs = N processes, key groups sharded by
 KeyGroupRangeAssignment.computeKeyGroupRangeForOperatorIndex, weak scaling (each rank
 generates the same number of events over the full key space).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) generates the stream, warms up, times
+the N steps and prints the result line.  --dump-outputs DIR also writes what the timed
+steps last handed their caller (DIR/<name>.npy).  Everything else the bench measures -- the CPU
+baseline, the host-fed leg, the algorithmic bytes behind the roofline fraction, the oracle
+check -- runs only with --full.
 
 Prints ONE JSON line on rank 0.
 """
@@ -32,6 +39,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+STRETCH_EVENTS = 1_000_000_000  # events of the stream generated (and held in HBM) at a time: 24 GB of columns
 INGEST_PATH = "region_buffered"  # the ingest pipeline a committed traffic.json must describe
 
 C1 = -7046029254386353131   # 0x9E3779B97F4A7C15 as int64
@@ -57,6 +65,20 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU "
+                         "baseline, the host-fed leg, the algorithmic bytes of the roofline fields (a pass "
+                         "over the timed batches) and, with --checksum --oracle-check, the oracle comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path last handed its caller -- the rows of the newest timed "
+                         "watermark that fired any (the last step's, when --steps is a multiple of the fire "
+                         "cycle), last_fired_{key,start,end,result}.npy -- and the rows the end of "
+                         "input then fires from the state the timed steps left, end_of_input_*.npy, as float64; "
+                         "each a fixed sample by key (see DUMP_KEY_MOD), sorted, with the full row count")
+    ap.add_argument("--stretch-steps", type=int, default=None,
+                    help="batches of the stream generated at a time (default: STRETCH_EVENTS events' worth, 100 at "
+                         "the default batch size, rounded to whole fire cycles); a run of more steps generates the "
+                         "next stretch between its steps, with the clock stopped")
     ap.add_argument("--agg", default="sum_i64")
     ap.add_argument("--keys", type=int, default=10_000_000)
     ap.add_argument("--events-per-pane", type=int, default=100_000_000, help="per GPU, per 2-s pane")
@@ -83,9 +105,9 @@ def parse(argv=None):
                     help="run the RCCL exchange path at N = 1 too (a one-rank communicator: every record comes "
                          "back to this rank) -- a check of the N > 1 code path on one GPU")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-host-fed", action="store_true",
-                    help="skip the host-fed leg (gw_ingest from host columns: pinned staging + H2D)")
+                    help="with --full: skip the host-fed leg (gw_ingest from host columns: pinned staging + H2D)")
     ap.add_argument("--host-fed-steps", type=int, default=21,
                     help="batches of the host-fed leg: the first fire cycle (10) untimed, as a running job's "
                          "buffers are grown by then; the other 11 include a 10M-row fire and drain")
@@ -97,15 +119,16 @@ def parse(argv=None):
                          "order-independent row checksum (oracle.rows_hash_sum) summed over steps and ranks "
                          "(a check, not a bench setting)")
     ap.add_argument("--oracle-check", action="store_true",
-                    help="with --checksum at N=1: also run the CPU oracle over the same stream and report "
+                    help="with --full --checksum at N=1: also run the CPU oracle over the same stream and report "
                          "per-watermark agreement (short runs only: the oracle does ~1-2M events/s)")
     return ap.parse_args(argv)
 
 
 def make_stream(nb, steps_total, K, E, slide, disorder, agg, dev, rank=0, world=1, key_partitioned=False,
-                maxp=128, t_shift=0):
+                maxp=128, t_shift=0, first=0):
     """The bench's synthetic Nexmark-Q5 bids in HBM: steps_total watermark batches of nb
-    events.  auction = splitmix64(i) mod K (uniform), ts advancing so each `slide` of event
+    events, batches first .. first + steps_total - 1 of the stream (event i of the stream is
+    the same whichever call generates it).  auction = splitmix64(i) mod K (uniform), ts advancing so each `slide` of event
     time holds E events with jitter <= disorder, value = splitmix64(i') mod 1e6.  With
     key_partitioned (N > 1, no exchange) the keys are drawn from this rank's key groups only
     (KeyGroupRangeAssignment.computeKeyGroupRangeForOperatorIndex), so every rank keeps the
@@ -114,8 +137,7 @@ def make_stream(nb, steps_total, K, E, slide, disorder, agg, dev, rank=0, world=
     maximum, identical on every rank.  t_shift (ms) moves the event-time origin back: the
     watermark of batch b then completes windows where batch b + t_shift / interval would have."""
     from flink_amd import _native as N
-    n_all = nb * steps_total
-    idx = torch.arange(n_all, device=dev, dtype=torch.int64)
+    idx = torch.arange(first * nb, (first + steps_total) * nb, device=dev, dtype=torch.int64)
     seed = 0x5EED0005 + 7919 * rank
     draw = splitmix64(idx, seed) & MASK63
     if key_partitioned and world > 1:
@@ -139,9 +161,15 @@ def make_stream(nb, steps_total, K, E, slide, disorder, agg, dev, rank=0, world=
         v = (splitmix64(idx, seed ^ 0x1234) & MASK63) % 1_000_000
         vals = v.to(torch.float64).view(torch.int64) if agg.endswith("f64") else v
     del idx, jitter
-    wms = [t0_ms + (((b + 1) * nb - 1) * slide) // E - disorder - 1 for b in range(steps_total)]
+    wms = watermarks(nb, first, steps_total, E, slide, disorder, t_shift)
     torch.cuda.synchronize()
     return keys, ts, vals, wms
+
+
+def watermarks(nb, first, steps, E, slide, disorder, t_shift=0):
+    """make_stream's watermarks of batches first .. first + steps - 1."""
+    t0_ms = 1_700_000_000_000 - t_shift
+    return [t0_ms + (((b + 1) * nb - 1) * slide) // E - disorder - 1 for b in range(first, first + steps)]
 
 
 def make_operator(W, N, args, K, world=1, rank=0, local=0, nb=None):
@@ -164,11 +192,13 @@ class Steps:
                  ahead=1):
         import ctypes
         self.op, self.N, self.ex, self.ex_stream = op, N, ex, ex_stream
-        self.keys, self.ts, self.vals, self.wms, self.nb = keys, ts, vals, wms, nb
+        self.wms, self.nb = wms, nb
         self.collect = collect
         self.per_wm = []  # (rows, checksum) per watermark when collecting
         self.keep_rows = keep_rows  # collect: also keep every watermark's rows (tests' row diff)
         self.rows = []
+        self.last_rows = None  # collect: the rows of the newest watermark
+        self.last_fired = None  # ... and of the newest one that fired any
         self.exch_bytes = 0
         self.begun = -1  # the last batch whose exchange has begun
         self.finished = -1  # ... and finished (its receive columns in self.ready until ingested)
@@ -183,13 +213,21 @@ class Steps:
         self._h, self._stream = op.handle, op.stream()
         self._fired = ctypes.c_int64(0)
         self._fired_ref = ctypes.byref(self._fired)
+        self.load(keys, ts, vals, 0)
+
+    def load(self, keys, ts, vals, base):
+        """The columns of batches base, base + 1, ... (a stream longer than the device holds is
+        generated a stretch at a time, between the clocked stretches of steps)."""
+        nb = self.nb
+        self.keys, self.ts, self.vals, self.base = keys, ts, vals, base
         es = keys.element_size()
-        self._ptrs = [(keys.data_ptr() + b * nb * es, ts.data_ptr() + b * nb * es,
-                       vals.data_ptr() + b * nb * es if vals is not None else None) for b in range(len(wms))]
+        self._ptrs = [(keys.data_ptr() + i * nb * es, ts.data_ptr() + i * nb * es,
+                       vals.data_ptr() + i * nb * es if vals is not None else None)
+                      for i in range(keys.numel() // nb)]
 
     def _begin(self, b):
         nb = self.nb
-        lo, hi = b * nb, (b + 1) * nb
+        lo, hi = (b - self.base) * nb, (b - self.base + 1) * nb
         v = self.vals[lo:hi] if self.vals is not None else None
         self.ex.begin(self.keys[lo:hi], self.ts[lo:hi], v, stream=self.ex_stream, wm=self.wms[b])
         self.begun = b
@@ -204,9 +242,10 @@ class Steps:
         self.finished += 1
         self.ready[self.finished] = (n, pk, pt, pv, wmin, ist, self.ex.last_words())
 
-    def step(self, b, timed=False, b_in=24, rank=0, last=None):
+    def step(self, b, timed=False, b_in=24, rank=0, last=None, hold=False):
         """One batch; returns the rows its watermark fired.  last: the last batch of this phase
-        (warmup / timed): the exchange begins and finishes batches up to it ahead of the ingest."""
+        (warmup / timed): the exchange begins and finishes batches up to it ahead of the ingest.
+        hold: leave the fired rows pending in the operator (the caller drains them later)."""
         op, nb, N = self.op, self.nb, self.N
         if self.ex is not None:
             # the native exchange on a stream of its own; the ingest orders through the receive
@@ -233,17 +272,21 @@ class Steps:
             wm = wmin
         else:
             # columns generated and synchronised before the clock: no producer ordering needed
-            pk, pt, pv = self._ptrs[b]
+            pk, pt, pv = self._ptrs[b - self.base]
             N.check(self._ingest(self._h, nb, pk, None, pt, pv, self._stream), self._h)
             wm = self.wms[b]
         N.check(self._advance(self._h, wm, self._fired_ref), self._h)
         fired = self._fired.value
-        self.consume()
+        if not hold:
+            self.consume()
         return fired
 
     def consume(self):
         if self.collect:
             rows = self.op.drain()
+            self.last_rows = rows
+            if len(rows[0]):
+                self.last_fired = rows
             self.per_wm.append((len(rows[0]), rows_checksum(rows)))
             if self.keep_rows:
                 self.rows.append(rows)
@@ -284,9 +327,32 @@ def main(argv=None):
     # timed steps is a whole cycle of slide / interval batches (a cycle cut by the start of the
     # clock would carry a flush over fewer batches than the steady state).
     t_shift = (args.warmup - 1) * args.wm_interval_ms if args.warmup >= 1 else 0
-    keys, ts, vals, wms = make_stream(nb, steps_total, K, E, slide, args.disorder_ms, agg, dev, rank, world,
-                                      key_partitioned=args.exchange == "none", maxp=maxp, t_shift=t_shift)
-    log(f"rank {rank}: generated {nb * steps_total} events ({nb * steps_total * b_in / 1e9:.1f} GB) "
+    wms = watermarks(nb, 0, steps_total, E, slide, args.disorder_ms, t_shift)
+    # A stream longer than the device should hold (--steps in the thousands) is generated a
+    # stretch of batches at a time, each before its steps and outside the clock, into the memory
+    # of the one before.  A stretch ends where a fire cycle of the timed steps ends: the clock
+    # stops right after a firing watermark, which has synchronised with the device anyway, and
+    # no flush is added.  A run that fits in one stretch is generated whole, up front.
+    cycle = max(1, slide // args.wm_interval_ms)
+    stretch = args.stretch_steps or max(1, STRETCH_EVENTS // nb)
+    stretch = max(cycle, stretch // cycle * cycle)
+    gen_s = [0.0]
+
+    def generate(lo):
+        """Batches lo .. hi - 1 of the stream; hi as above."""
+        hi = min(steps_total, lo + stretch)
+        if args.warmup < hi < steps_total:
+            hi -= (hi - args.warmup) % cycle
+        t = time.time()
+        cols = make_stream(nb, hi - lo, K, E, slide, args.disorder_ms, agg, dev, rank, world,
+                           key_partitioned=args.exchange == "none", maxp=maxp, t_shift=t_shift, first=lo)[:3]
+        gen_s[0] += time.time() - t
+        return cols, hi
+
+    (keys, ts, vals), have = generate(0)
+    if args.oracle_check and have < steps_total:
+        raise SystemExit(f"--oracle-check runs the CPU oracle over the whole stream: at most {have} steps in all")
+    log(f"rank {rank}: generated {nb * have} of {nb * steps_total} events ({nb * have * b_in / 1e9:.1f} GB) "
         f"in {time.time() - t_gen:.1f}s")
 
     op = make_operator(W, N, args, K, world, rank, local, nb)
@@ -307,40 +373,85 @@ def main(argv=None):
     # pass 1 timed on every 4th batch (all batches are alike): two event records per timed launch
     # cost host time between batches; the fire and flush timers run on every launch
     op.enable_kernel_timing(0 if args.no_kernel_timing else 4)
-    for b in range(args.warmup):
-        run.step(b, last=args.warmup - 1)
+    def next_stretch(b):
+        """Batch b is the first one not in HBM: the next stretch replaces the present one (every
+        step so far has finished with its columns: the device is idle)."""
+        nonlocal keys, ts, vals, have
+        torch.cuda.synchronize()
+        keys = ts = vals = None
+        run.keys = run.ts = run.vals = None
+        (keys, ts, vals), have = generate(b)
+        run.load(keys, ts, vals, b)
+
+    b = 0
+    while b < args.warmup:
+        if b == have:
+            next_stretch(b)
+        end = min(have, args.warmup)
+        for b in range(b, end):
+            run.step(b, last=end - 1)
+        b = end
     op.flush()  # warmup batches still buffered are applied outside the timed region
     for w in (0, 1, 2):
         op.kernel_time_ms(w)  # reset timers after warmup
     st0 = op.stats()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    last = t0
     # Per fire cycle: a watermark that completes windows fires them and synchronises with
     # the device (gw_advance_watermark), so the host clock at the return of such a step
     # closes one cycle of batches + their fire.
     cycles = []
-    cyc_t, cyc_steps = t0, 0
-    for b in range(args.warmup, steps_total):
-        fired = run.step(b, True, b_in, rank, last=steps_total - 1)
-        cyc_steps += 1
-        if fired:  # the watermark completed windows: gw_advance_watermark fired them and synchronised
-            now = time.perf_counter()
-            cycles.append({"steps": cyc_steps, "ms": (now - cyc_t) * 1e3,
-                           "events_per_s": cyc_steps * nb / max(now - cyc_t, 1e-9)})
-            cyc_t, cyc_steps = now, 0
-            if rank == 0 and now - last > 30:
-                last = now
-                log(f"step {b - args.warmup + 1}/{args.steps}")
-    op.flush()  # every timed batch is in the window state when the clock stops
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    cyc_s, cyc_steps = 0.0, 0
+    # --dump-outputs: the rows of the newest timed watermark that fires any (every cycle-th one;
+    # the watermarks after it complete no window) stay pending from that step on (no
+    # gw_clear_rows, a host-side reset) and are drained after the clock; with --checksum every
+    # step drains its rows anyway
+    nwin = [(w + 1 - size) // slide for w in wms]  # windows complete at each watermark
+    firing = [i for i in range(max(args.warmup, 1), steps_total) if nwin[i] > nwin[i - 1]]
+    b_hold = firing[-1] if firing and args.dump_outputs and not args.checksum else steps_total
+    run.last_fired = None
+    g = int(np.gcd(size, slide))
+    dsum = 0
+    elapsed = 0.0  # the clock runs over the steps of each stretch, not over the generation between
+    last = time.perf_counter()
+    b = args.warmup
+    while b < steps_total:
+        if b == have:
+            next_stretch(b)
+        end = have
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        cyc_t = t0
+        for b in range(b, end):
+            fired = run.step(b, True, b_in, rank, last=end - 1, hold=b >= b_hold)
+            cyc_steps += 1
+            if fired:  # the watermark completed windows: gw_advance_watermark fired them and synchronised
+                now = time.perf_counter()
+                cyc_s += now - cyc_t
+                cycles.append({"steps": cyc_steps, "ms": cyc_s * 1e3, "events_per_s": cyc_steps * nb / max(cyc_s, 1e-9)})
+                cyc_t, cyc_s, cyc_steps = now, 0.0, 0
+                if rank == 0 and now - last > 30:
+                    last = now
+                    log(f"step {b - args.warmup + 1}/{args.steps}")
+        b = end
+        if b == steps_total:
+            op.flush()  # every timed batch is in the window state when the clock stops
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        now = time.perf_counter()
+        elapsed += now - t0
+        cyc_s += now - cyc_t
+        if args.full:
+            # ---------------------------------- algorithmic bytes (SURVEY.md §8d)
+            # D_b: distinct (key, pane) accumulators each timed batch touches.  Exact on the
+            # rank's own generated batches (N=1: the ingested batch itself).
+            for i in range(max(args.warmup, run.base) - run.base, end - run.base):
+                lo, hi = i * nb, (i + 1) * nb
+                comp = keys[lo:hi] * 4096 + ((ts[lo:hi] // g) % 4096)
+                dsum += int(torch.unique(comp).numel())
     if cyc_steps:
-        cycles.append({"steps": cyc_steps, "ms": (time.perf_counter() - cyc_t) * 1e3, "partial": True})
+        cycles.append({"steps": cyc_steps, "ms": cyc_s * 1e3, "partial": True})
     if dist:
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
@@ -351,47 +462,73 @@ def main(argv=None):
     st1 = op.stats()
     events_rank = nb * args.steps
     rows_rank = st1["rows_fired"] - st0["rows_fired"]
+    last_rows = None
+    if args.dump_outputs:  # the newest rows the timed steps handed their caller
+        last_rows = run.last_fired if args.checksum else op.drain()
 
-    # ------------------------------------------ algorithmic bytes
-    # D_b: distinct (key, pane) accumulators each timed batch touches.  Exact on the
-    # rank's own generated batches (N=1: the ingested batch itself).
-    g = int(np.gcd(size, slide))
-    dsum = 0
-    for b in range(args.warmup, steps_total):
-        lo, hi = b * nb, (b + 1) * nb
-        comp = keys[lo:hi] * 4096 + ((ts[lo:hi] // g) % 4096)
-        dsum += int(torch.unique(comp).numel())
-    ingest_bytes_total = events_rank * b_in + 2 * s_acc * dsum
-    fire_bytes_total = rows_rank * (32 + s_acc)
     # The ingest pipeline of one watermark batch: pass 1 per batch (its average over the timed
     # sample of batches) plus its share of the plan / pass 2 / apply launches, which run once
     # per buffer flush.  Device time from HIP events on the operator's stream.
     pipe_ms_total = ingest_ms * args.steps + apply_ms * apply_launches
-    per_launch = ingest_bytes_total / max(args.steps, 1)
     pipe_ms = pipe_ms_total / max(args.steps, 1)
-    achieved = ingest_bytes_total / (pipe_ms_total / 1e3) / 1e9 if pipe_ms_total > 0 else 0.0
-    pipeline_gbs = (ingest_bytes_total + fire_bytes_total) / elapsed / 1e9
+    roofline = {
+        "bound": "hbm",
+        "kernel": "ingest pipeline per watermark batch (region path: pass 1 k_rgn_p1 per batch + "
+                  "plan / pass 2 / k_rgn_apply per buffer flush)",
+        "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "avg_launch_ms": pipe_ms, "launches": args.steps,
+        "pass1_timed_launches": ingest_launches,
+        "pass1_avg_ms": ingest_ms, "apply_avg_ms": apply_ms, "apply_launches": apply_launches,
+        "fire_avg_launch_ms": fire_ms, "fire_launches": fire_launches,
+    }
+    if args.full:  # the algorithmic bytes, from the D_b counted above
+        ingest_bytes_total = events_rank * b_in + 2 * s_acc * dsum
+        fire_bytes_total = rows_rank * (32 + s_acc)
+        achieved = ingest_bytes_total / (pipe_ms_total / 1e3) / 1e9 if pipe_ms_total > 0 else 0.0
+        pipeline_gbs = (ingest_bytes_total + fire_bytes_total) / elapsed / 1e9
+        roofline.update({
+            "achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes(agg, nb),
+            "bytes_per_launch": ingest_bytes_total / max(args.steps, 1),
+            "pipeline_achieved": pipeline_gbs, "pipeline_frac": pipeline_gbs / HBM_PEAK_GBS,
+            "d_over_n": dsum / max(events_rank, 1),
+        })
 
     checksum = None
-    if args.checksum:
+    final_rows = None
+    if args.checksum or args.dump_outputs:
         op.advance_watermark(W.LONG_MAX)  # end of input: everything left fires (outside the clock)
-        run.consume()
-        checksum = wrap64(sum(c for _, c in run.per_wm))
+        if args.checksum:
+            run.consume()
+            final_rows = run.last_rows
+            checksum = wrap64(sum(c for _, c in run.per_wm))
+        else:
+            final_rows = op.drain()
+    if args.dump_outputs:
+        sfx = f".rank{rank}" if world > 1 else ""
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump_rows(args.dump_outputs, "last_fired", sfx, last_rows)
+        dump_rows(args.dump_outputs, "end_of_input", sfx, final_rows)
+    del last_rows, final_rows
     tot = torch.tensor([events_rank, rows_rank, checksum or 0], dtype=torch.int64, device=dev)
     if dist:
         dist.all_reduce(tot)
     events_all, rows_all = int(tot[0].item()), int(tot[1].item())
     value = events_all / elapsed
 
-    # ------------------------------------------------------------ CPU baseline
+    # ------------------------------------------------- --full: CPU baseline, host-fed leg
+    # (over the head of the stream: its first stretch, generated again after a longer run)
+    if args.full and rank == 0 and world == 1:
+        if run.base != 0:
+            next_stretch(0)
+        wms = wms[:have]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, keys, ts, vals, wms, nb, agg, size, slide)
     host_fed = None
-    if rank == 0 and world == 1 and not args.no_host_fed:
+    if args.full and rank == 0 and world == 1 and not args.no_host_fed:
         host_fed = host_fed_leg(args, W, keys, ts, vals, wms, nb, agg, size, slide, K, maxp, local)
     oracle_check = None
-    if rank == 0 and world == 1 and args.checksum and args.oracle_check:
+    if args.full and rank == 0 and world == 1 and args.checksum and args.oracle_check:
         oracle_check = oracle_watermarks(args, keys, ts, vals, wms, nb, run.per_wm)
 
     if rank == 0:
@@ -408,6 +545,7 @@ def main(argv=None):
             "vs_baseline": None,
             "dtype": "f64" if agg.endswith("f64") else "int64",
             "data": "synthetic (splitmix64 Nexmark-Q5-shaped bids, generated in HBM)",
+            "stretch_steps": stretch, "generate_seconds": gen_s[0],
             "config": {
                 "workload": f"nexmark_q5_sliding_{size // 1000}s_{slide // 1000}s_{agg}",
                 "keys": K, "events_per_pane_per_gpu": E, "events_per_step_per_gpu": nb,
@@ -416,19 +554,8 @@ def main(argv=None):
                 "aggregate": agg, "max_parallelism": maxp,
                 "parallelism": f"keygroup-sharded x{world}" + (f" ({args.exchange} exchange)" if world > 1 else ""),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "ingest pipeline per watermark batch (region path: pass 1 k_rgn_p1 per batch + "
-                          "plan / pass 2 / k_rgn_apply per buffer flush)",
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes(agg, nb),
-                "bytes_per_launch": per_launch, "avg_launch_ms": pipe_ms, "launches": args.steps,
-                "pass1_timed_launches": ingest_launches,
-                "pass1_avg_ms": ingest_ms, "apply_avg_ms": apply_ms, "apply_launches": apply_launches,
-                "pipeline_achieved": pipeline_gbs, "pipeline_frac": pipeline_gbs / HBM_PEAK_GBS,
-                "fire_avg_launch_ms": fire_ms, "fire_launches": fire_launches,
-                "d_over_n": dsum / max(events_rank, 1),
-            },
+            "full": args.full,
+            "roofline": roofline,  # the byte-derived fields (achieved, frac, ...) only with --full
             "rows_fired": rows_all,
             "fire_cycles": cycles,
             "host_fed": host_fed,
@@ -475,6 +602,35 @@ def oracle_watermarks(args, keys, ts, vals, wms, nb, per_wm):
     return {"watermarks": len(ora), "match": not bad and len(per_wm) == len(ora), "mismatched": bad[:10],
             "oracle_checksum": wrap64(sum(c for _, c in ora)),
             "oracle_seconds": sec, "oracle_threads": threads}
+
+
+DUMP_KEY_MOD = 64         # --dump-outputs keeps the rows of one key in 64 (by a hash of the key) ...
+DUMP_MAX_ROWS = 900_000   # ... and at most this many of them per file set: < 64 MB for both sets
+
+
+def dump_rows(out_dir, name, sfx, rows):
+    """--dump-outputs: one set of fired rows as <name>_{key,start,end,result}<sfx>.npy (float64;
+    keys, window bounds and the bench's integer sums are exact in it) and <name>_count<sfx>.npy =
+    [rows fired, rows written].  Up to DUMP_MAX_ROWS rows are all written; of more, a sample.  The
+    fire emits rows in no fixed order, so the sample is chosen by key -- the rows whose key hashes
+    to 0 mod DUMP_KEY_MOD -- and every set is sorted by (key, start, end); of a sample beyond
+    DUMP_MAX_ROWS the lowest rows are kept.  The same build and arguments give the same
+    files byte for byte.  A set without rows (no timed watermark fired: fewer timed steps than a
+    fire cycle) writes its count alone, never an empty column."""
+    np.save(os.path.join(out_dir, f"{name}_count{sfx}.npy"), np.zeros(2))
+    if rows is None or not len(rows[0]):
+        return
+    k, s, e, r = rows
+    n = len(k)
+    if n > DUMP_MAX_ROWS:
+        with np.errstate(over="ignore"):
+            sel = ((k.view(np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(32)) % np.uint64(DUMP_KEY_MOD) == 0
+        if sel.any():
+            k, s, e, r = k[sel], s[sel], e[sel], r[sel]
+    order = np.lexsort((r, e, s, k))[:DUMP_MAX_ROWS]
+    for col, a in (("key", k), ("start", s), ("end", e), ("result", r)):
+        np.save(os.path.join(out_dir, f"{name}_{col}{sfx}.npy"), a[order].astype(np.float64))
+    np.save(os.path.join(out_dir, f"{name}_count{sfx}.npy"), np.array([n, len(order)], np.float64))
 
 
 def rows_checksum(rows) -> int:
