@@ -214,6 +214,17 @@ struct IngestArgs {
     unsigned long long st_seq;      //     and the stamp it writes last
     uint64_t ring_fresh;            // ring positions holding only identities (not in occ)
     int32_t stale;                  // lazily retired cells may hold stale values behind clear presence bits
+    // fused fire (k_rgn_apply_nar<AGG, true, true>, gw_runtime.cpp fast_fire): the apply emits the
+    // rows of the one window [f_start, f_end) over ring positions f_wmask before it retires
+    int32_t fire;
+    uint64_t f_wmask;
+    int64_t f_start;
+    int64_t f_end;
+    int64_t* o_key;
+    int64_t* o_start;
+    int64_t* o_end;
+    int64_t* o_res;
+    int64_t o_cap;                  // rows the output arrays hold
 };
 
 #ifndef GW_PART_TILE
@@ -367,8 +378,15 @@ struct FireGuard {
     int64_t o_cap;
     int64_t nwin;
     int64_t reset_rows;  // first zero the row cursor (a gw_clear_rows the host deferred to here)
+    // 1: the guard behind a fused fire (k_rgn_apply_nar emitted the rows; the guard before that
+    // launch did the tests above on what was knowable then): the fire stays revoked, or is
+    // revoked by what the apply left -- spills, wide records, a full table, deferred entries --
+    // and then the row cursor goes back to fire_rows0
+    int64_t after;
 };
 hipError_t launch_fire_guard(DevStatus* st, const FireGuard& g, hipStream_t s);
+// The retire of a fused fire (a.rmask; nothing when st->fire_skip is set), behind that guard.
+hipError_t launch_fire_retire(const FireArgs& a, hipStream_t s);
 // Cells of ring positions `pmask` whose presence bit is clear -> the identity (the retires a
 // lazy fire left behind, before a kernel that adds into cells with device atomics)
 hipError_t launch_clean_stale(const PaneTable& t, uint64_t pmask, hipStream_t s);

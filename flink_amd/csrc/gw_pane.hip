@@ -1580,16 +1580,34 @@ constexpr int kNarLoadU = 4;  // 16-B state loads per thread in flight together
 #ifndef GW_NAR_DEPTH
 #define GW_NAR_DEPTH 2  // record steps whose loads are in flight (2: one ahead of the applied one)
 #endif
+#ifndef GW_FIRE_U
+#define GW_FIRE_U 2  // fused fire: 64-slot chunks a wave folds per step
+#endif
 
 __device__ __forceinline__ uint32_t k32_of(int64_t k) {
     return k == kEmptyKey ? kK32Empty : ((uint64_t)k < (uint64_t)kK32Foreign ? (uint32_t)k : kK32Foreign);
 }
 
+// The aggregates whose apply can fire (FIRE below): one-word cells that retire by their
+// presence bits alone (the lazily retired integer sums) or carry the presence themselves (COUNT).
+template <int AGG>
+__device__ __forceinline__ constexpr bool fire_agg() {
+    return AGG == GW_SUM_I64 || AGG == GW_SUM_I32 || AGG == GW_COUNT;
+}
+
 // STALE: cells behind clear presence bits may hold stale values (lazy fire retires, FireArgs::
 // lazy_retire) and are staged as the identity; without it the staging is a plain copy.
-template <int AGG, bool STALE>
+// FIRE (the fused fire, gw_runtime.cpp fast_fire): before the workgroup retires it emits the rows
+// of the one window a.f_wmask for every slot of its super-region -- the keys, the presence masks
+// and the pane applied last are still in LDS; the window's other panes are read from HBM -- by
+// the rule of k_fire2::fold, and changes no state doing so (the retire follows in k_fire_retire
+// once k_fire_guard has seen what this launch left; rows of a revoked fire are dropped by
+// putting the row cursor back).  Rows are reserved with ONE device atomic per workgroup: the
+// folded results replace the LDS pane in place, a scan of the per-wave-chunk row counts gives
+// every row its place.
+template <int AGG, bool STALE, bool FIRE = false>
 __global__ void __launch_bounds__(kApplyThreads) GW_APPLY_ATTR k_rgn_apply_nar(IngestArgs a) {
-    if constexpr (!cmp_agg<AGG>()) {
+    if constexpr (!cmp_agg<AGG>() || (FIRE && !fire_agg<AGG>())) {
         return;
     } else {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1653,7 +1671,9 @@ __global__ void __launch_bounds__(kApplyThreads) GW_APPLY_ATTR k_rgn_apply_nar(I
     }
     __syncthreads();
     const uint32_t pmask = s_pos;
-    if (!pmask) return;  // uniform
+    // uniform; a firing apply goes on: keys whose last records sit in older panes of the window
+    // still have a row
+    if (!pmask && !FIRE) return;
 
     // keys (int64 in HBM -> 32-bit in LDS) and presence masks of the F regions
     {
@@ -1962,7 +1982,7 @@ __global__ void __launch_bounds__(kApplyThreads) GW_APPLY_ATTR k_rgn_apply_nar(I
     }
     __syncthreads();
     // write back: the masks whole, the keys of dirty lines (a foreign slot never changes)
-    if constexpr (M) {
+    if (M && pmask) {
         const int per = S / 16, lper = l2S - 4;
         for (int w = threadIdx.x; w < FS / 16; w += blockDim.x) {
             const int d = w >> lper;
@@ -1982,6 +2002,136 @@ __global__ void __launch_bounds__(kApplyThreads) GW_APPLY_ATTR k_rgn_apply_nar(I
     spills = wave_sum(spills);
     if (__lane_id() == 0 && spills) atomicAdd(&a.st->spills, spills);
     block_commit(a.st, 0, ins, flags, 0);
+    if constexpr (FIRE) {
+        static_assert(W == 1 && kNarMaxSlots / 64 <= kApplyRuns && kNarMaxSlots / 64 <= 128, "fused fire geometry");
+        uint32_t* s_fc = r_cnt;  // rows of each 64-slot chunk, then their exclusive scan
+        __shared__ unsigned long long s_fbase;
+        // a guard before this launch (no room for the rows, something deferred) or a workgroup
+        // whose rows did not fit has revoked the fire
+        if (threadIdx.x == 0) s_fbase = *(volatile unsigned long long*)&a.st->fire_skip;
+        __threadfence_block();
+        __syncthreads();  // and the panes this workgroup wrote back above are re-read below
+        if (s_fbase) return;  // uniform
+        const uint64_t wm = a.f_wmask;
+        const int npos = __popcll(wm);
+        const int lp = pmask ? 31 - __clz((int)pmask) : -1;  // the pane in lcell
+        int posl[6];
+        {
+            uint64_t need = wm;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                posl[q] = need ? __ffsll((long long)need) - 1 : 0;
+                need &= need - 1;
+            }
+        }
+        const int nchunk = FS >> 6;
+        constexpr int FU = GW_FIRE_U;  // chunks per wave and step: their loads are in flight together
+        for (int c0 = wave; c0 < nchunk; c0 += FU * nw) {
+            int64_t v[FU][6];
+#pragma unroll
+            for (int u = 0; u < FU; ++u) {
+                const int c = c0 + u * nw;
+                const int slot = min(c, nchunk - 1) << 6 | lane;  // unconditional loads
+                const int64_t g = ((sr * F + (slot >> l2S)) << l2S) | (slot & (S - 1));
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    v[u][q] = id0;
+                    if (q < npos && posl[q] != lp) v[u][q] = __builtin_nontemporal_load(pt_cell(a.t, g, posl[q]));  // uniform
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < FU; ++u) {
+                const int c = c0 + u * nw;
+                if (c >= nchunk) break;  // uniform
+                const int slot = c << 6 | lane;
+                const uint32_t mb = M ? lmask[slot] : 0u;
+                const int64_t vl = lcell[slot];
+                int64_t r0 = id0, r1 = 0;
+                bool any = false;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    if (q >= npos) break;  // uniform
+                    const int64_t x = posl[q] == lp ? vl : v[u][q];
+                    const bool pres = M ? ((mb >> posl[q]) & 1) != 0 : x != 0;
+                    if (pres) {
+                        fold_cell(AGG, r0, r1, x, 0);
+                        any = true;
+                    }
+                }
+                lcell[slot] = any ? cell_result(AGG, r0, r1) : 0;  // only this lane reads or writes the slot
+                const uint64_t bal = __ballot(any);
+                if (lane == 0) s_fc[c] = (uint32_t)__popcll(bal);
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const uint32_t n0 = 2 * lane < nchunk ? s_fc[2 * lane] : 0u;
+            const uint32_t n1 = 2 * lane + 1 < nchunk ? s_fc[2 * lane + 1] : 0u;
+            uint32_t incl = n0 + n1;
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = __shfl_up(incl, o);
+                if (lane >= o) incl += up;
+            }
+            s_fc[2 * lane] = incl - n0 - n1;
+            s_fc[2 * lane + 1] = incl - n1;
+            if (lane == 63) {
+                unsigned long long base = 0;
+                if (incl) {
+                    base = atomicAdd(&a.st->rows, (unsigned long long)incl);
+                    if (base + incl > (unsigned long long)a.o_cap) {  // no room: revoke the fire
+                        atomicExch(&a.st->fire_skip, 1ull);
+                        base = ~0ull;
+                    }
+                }
+                s_fbase = base;
+            }
+        }
+        // the sentinel slot (the key Long.MIN_VALUE, no narrow record's) belongs to no super-region
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const int64_t g = a.t.cap;
+            const uint64_t mb = M ? pt_mask_get(a.t, g) : ~0ull;
+            int64_t r0 = id0, r1 = 0;
+            bool any = false;
+            for (uint64_t q = wm; q; q &= q - 1) {
+                const int pos = __ffsll((long long)q) - 1;
+                const int64_t x = *pt_cell(a.t, g, pos);
+                if (M ? ((mb >> pos) & 1) != 0 : x != 0) {
+                    fold_cell(AGG, r0, r1, x, 0);
+                    any = true;
+                }
+            }
+            if (any) {
+                const unsigned long long j = atomicAdd(&a.st->rows, 1ull);
+                if (j < (unsigned long long)a.o_cap) {
+                    a.o_key[j] = kEmptyKey;
+                    a.o_start[j] = a.f_start;
+                    a.o_end[j] = a.f_end;
+                    a.o_res[j] = cell_result(AGG, r0, r1);
+                } else {
+                    atomicExch(&a.st->fire_skip, 1ull);
+                }
+            }
+        }
+        __syncthreads();
+        const unsigned long long base = s_fbase;
+        if (base == ~0ull) return;  // uniform
+        for (int c = wave; c < nchunk; c += nw) {
+            const int slot = c << 6 | lane;
+            const int64_t res = lcell[slot];
+            const bool any = M ? (lmask[slot] & wm) != 0 : res != 0;
+            const uint64_t bal = __ballot(any);
+            if (any) {
+                const unsigned long long j = base + s_fc[c] + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+                const uint32_t k = lkeys[slot];
+                const int64_t k64 = k == kK32Foreign ? pt_region(a.t, sr * F + (slot >> l2S))[slot & (S - 1)] : (int64_t)k;
+                // read once and written once: kept out of the caches the apply beside it lives on
+                __builtin_nontemporal_store(k64, &a.o_key[j]);
+                __builtin_nontemporal_store(a.f_start, &a.o_start[j]);
+                __builtin_nontemporal_store(a.f_end, &a.o_end[j]);
+                __builtin_nontemporal_store(res, &a.o_res[j]);
+            }
+        }
+    }
     }
 }
 
@@ -2567,7 +2717,15 @@ __global__ void __launch_bounds__(64) k_fire_guard(DevStatus* st, FireGuard g) {
     }
     flags = wave_ior(flags);
     used = wave_sum(used);
-    if (lane == 0) {
+    if (lane == 0 && g.after) {
+        // behind a fused fire (k_rgn_apply_nar<AGG, true, true>): what that launch itself left.  Its
+        // rows are speculative until here: a revoked fire's rows go by putting the cursor back
+        const bool skip = st->fire_skip != 0 || st->spills != 0 || st->wide_vals != 0 ||
+                          (flags & (GW_DF_TABLE_FULL | GW_DF_NO_TS | GW_DF_RANGE)) != 0 ||
+                          st->n_deferred != g.expect_ndef;
+        if (skip) st->rows = st->fire_rows0;
+        st->fire_skip = skip ? 1ull : 0ull;
+    } else if (lane == 0) {
         if (g.reset_rows) st->rows = 0;
         const unsigned long long rows = g.reset_rows ? 0ull : st->rows;
         const bool skip = st->spills != 0 || st->wide_vals != 0 ||
@@ -2576,6 +2734,52 @@ __global__ void __launch_bounds__(64) k_fire_guard(DevStatus* st, FireGuard g) {
                           (int64_t)rows + g.nwin * ((int64_t)used + 1) > g.o_cap;
         st->fire_skip = skip ? 1ull : 0ull;
         st->fire_rows0 = rows;
+    }
+}
+
+// The retire of a fused fire (k_rgn_apply_nar<AGG, true, true> emitted the rows and changed no
+// state), behind the guard that followed it: what k_fire2 does for a.rmask -- the presence bits
+// cleared (the mask arrays alone, whole words), the cells reset where the presence bits are not
+// the retire (COUNT), the sentinel slot reset for real, the occupancy shards cleared.
+template <int AGG>
+__global__ void __launch_bounds__(256) k_fire_retire(FireArgs a) {
+    if (*(volatile unsigned long long*)&a.st->fire_skip) return;  // uniform: set before this launch
+    constexpr bool M = uses_mask<AGG>();
+    constexpr int W = (AGG == GW_AVG_I64 || AGG == GW_AVG_F64) ? 2 : 1;
+    if (blockIdx.x == 0 && threadIdx.x < kShards) atomicAnd(&a.st->sh[threadIdx.x].occ, ~a.rmask);
+    if (!a.rmask) return;
+    const int64_t id0 = identity0(AGG);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t0 == 0) {
+        const int64_t g = a.t.cap;
+        if constexpr (M) pt_mask_put(a.t, g, pt_mask_get(a.t, g) & ~a.rmask);
+        for (uint64_t m = a.rmask; m; m &= m - 1) {
+            int64_t* c = pt_cell(a.t, g, __ffsll((long long)m) - 1);
+            c[0] = id0;
+            if (W == 2) c[1] = 0;
+        }
+    }
+    if constexpr (M) {
+        // a slot's mask is 1 << mask_shift bytes: the retired bits replicated over a 64-bit word
+        uint64_t rep = a.rmask;
+        for (int b = 8 << a.t.mask_shift; b < 64; b <<= 1) rep |= rep << b;
+        const int64_t MW = pt_mask_words(a.t);
+        for (int64_t i = t0; i < a.t.nreg * MW; i += stride) {
+            const int64_t r = i / MW;
+            uint64_t* p = reinterpret_cast<uint64_t*>(pt_mask_base(a.t, r)) + (i - r * MW);
+            const uint64_t v = *p;
+            if (v & rep) *p = v & ~rep;
+        }
+    }
+    if (!(M && a.lazy_retire)) {
+        for (uint64_t m = a.rmask; m; m &= m - 1) {
+            const int pos = __ffsll((long long)m) - 1;
+            for (int64_t g = t0; g < a.t.cap; g += stride) {
+                int64_t* c = pt_cell(a.t, g, pos);
+                c[0] = id0;
+                if (W == 2) c[1] = 0;
+            }
+        }
     }
 }
 
@@ -2897,7 +3101,11 @@ hipError_t launch_region_flush(const IngestArgs& a, hipStream_t s, hipEvent_t e0
         hipLaunchKernelGGL((k_rgn_p2<A, kFmtNar>), dim3((unsigned)(a.ngroups * nb1)), dim3(kPartThreads), part_lds, \
                            s, a);                                                                               \
     }                                                                                                           \
-    if (a.stale)                                                                                                \
+    if (a.fire) {                                                                                               \
+        lds_opt_in((const void*)k_rgn_apply_nar<A, true, true>, lds);                                          \
+        GW_TLAUNCH((k_rgn_apply_nar<A, true, true>), dim3((unsigned)(a.t.nreg >> a.sr_bits)),                  \
+                   dim3(kApplyThreads), lds, s, a.cur_empty ? e0 : nullptr, e1, a);                             \
+    } else if (a.stale)                                                                                         \
         GW_TLAUNCH((k_rgn_apply_nar<A, true>), dim3((unsigned)(a.t.nreg >> a.sr_bits)), dim3(kApplyThreads), lds, \
                    s, a.cur_empty ? e0 : nullptr, e1, a);                                                       \
     else                                                                                                        \
@@ -2992,6 +3200,14 @@ hipError_t launch_fire(const FireArgs& a, hipStream_t s, hipEvent_t e0, hipEvent
 
 hipError_t launch_fire_guard(DevStatus* st, const FireGuard& g, hipStream_t s) {
     hipLaunchKernelGGL(k_fire_guard, dim3(1), dim3(64), 0, s, st, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_fire_retire(const FireArgs& a, hipStream_t s) {
+    const int64_t n = a.t.has_mask && a.lazy_retire ? a.t.nreg * pt_mask_words(a.t) : a.t.cap;
+#define L(A) hipLaunchKernelGGL(k_fire_retire<A>, dim3(grid_for(n)), dim3(256), 0, s, a)
+    GW_AGG_SWITCH(a.t.agg, L);
+#undef L
     return hipGetLastError();
 }
 

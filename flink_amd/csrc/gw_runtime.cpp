@@ -1394,7 +1394,9 @@ struct gw_handle {
         if ((rc = refresh())) return rc;
         return flush_post(pf);
     }
-    int flush_launch(uint64_t apply_mask, PendingFlush& pf, bool& launched) {
+    // fuse (fast_fire): the fire whose rows this flush's apply emits itself, behind a guard
+    // launched here; *fuse is cleared when the flush turns out not to be a nar2 flush.
+    int flush_launch(uint64_t apply_mask, PendingFlush& pf, bool& launched, const FireArgs** fuse = nullptr) {
         launched = false;
         if (!nseg && !carry_on) return GW_OK;
         int rc;
@@ -1435,6 +1437,21 @@ struct gw_handle {
             carry_on = true;
             carry_mask = carry_next;
             eset ^= 1;
+        }
+        if (fuse && *fuse && !(a.nar2 && a.fmt == 2)) *fuse = nullptr;
+        if (fuse && *fuse) {
+            const FireArgs& f = **fuse;
+            a.fire = 1;
+            a.f_wmask = f.wmask[0];
+            a.f_start = f.start0;
+            a.f_end = f.start0 + f.size;
+            a.o_key = o_key; a.o_start = o_start; a.o_end = o_end; a.o_res = o_res;
+            a.o_cap = o_cap;
+            // what is knowable before the apply: room for a row per key seen so far, nothing
+            // deferred, no leftovers of an earlier flush
+            FireGuard g{0, o_cap, 1, rows_reset_pending ? 1 : 0};
+            rows_reset_pending = false;  // the guard zeroes the cursor
+            HIPCHECK(launch_fire_guard(d_st, g, stream));
         }
         if (timing) {
             auto ev = t_apply.get();
@@ -2693,6 +2710,8 @@ struct gw_handle {
 #define GW_FAST_FIRE 1  // 0: every fire after a flush waits for the flush's status first
 #endif
     int64_t fast_fires = 0;  // fires enqueued behind their flush (gw_kernel_time_ms which = 3)
+    int64_t fused_fires = 0;  // those of them whose rows the flush's apply emitted (which = 4)
+    int64_t fused_revoked = 0;  // fused fires a guard or a full row buffer revoked (which = 5)
     // The common fire -- no lateness, no restored windows, nothing deferred, one pass of
     // windows starting at fired_k -- enqueued right behind the flush that precedes it, with
     // k_fire_guard between them: ONE host round trip per watermark instead of two (the flush's
@@ -2718,7 +2737,24 @@ struct gw_handle {
         }
         PendingFlush pf;
         bool launched = false;
-        if ((rc = flush_launch(need, pf, launched))) return rc;
+        // The fused fire: one window of an aggregate whose apply can fire (the lazily retired
+        // integer sums, COUNT), behind a nar2 flush -- k_rgn_apply_nar emits the rows itself and
+        // no k_fire2 follows.  The fire's arguments do not depend on the flush, so they are made
+        // first, at the ring base the fire will have.  GW_FUSED_FIRE=0: always k_fire2.
+        static const bool fused_off = [] { const char* e = getenv("GW_FUSED_FIRE"); return e && atoi(e) == 0; }();
+        const FireArgs* fuse = nullptr;
+        FireArgs ff{};
+        if (!fused_off && kt == k_first && (nseg || carry_on) && n <= 6 &&
+            (cfg.agg == GW_COUNT || (tv.has_mask && (cfg.agg == GW_SUM_I64 || cfg.agg == GW_SUM_I32)))) {
+            const i128 Bs = B;
+            i128 keep_;
+            B = k_first * m;
+            rc = fire_args(k_first, kt, (kt + 1) * m, ff, keep_);
+            B = Bs;
+            if (rc) return rc;
+            fuse = &ff;
+        }
+        if ((rc = flush_launch(need, pf, launched, &fuse))) return rc;
         const i128 B0 = B;
         const uint64_t stale0 = stale_pos;
         B = k_first * m;  // rebase(k_first * m) without an eviction
@@ -2728,6 +2764,27 @@ struct gw_handle {
         f.o_key = o_key; f.o_start = o_start; f.o_end = o_end; f.o_res = o_res;
         f.guarded = 1;
         lazy_retire(f);
+        if (fuse && launched) {
+            FireGuard g2{0, o_cap, 1, 0, 1};
+            HIPCHECK(launch_fire_guard(d_st, g2, stream));
+            HIPCHECK(launch_fire_retire(f, stream));
+            dirty = true;
+            if ((rc = refresh())) return rc;
+            if (!h_st->fire_skip) {
+                fired(f, kt, keep);
+                dirty = false;  // the refresh above followed the retire
+                occ = h_st->occ;
+                fast_fires++;
+                fused_fires++;
+                done = true;
+                return GW_OK;
+            }
+            // revoked: the rows are gone and no state has changed; the exact path fires
+            fused_revoked++;
+            B = B0;
+            stale_pos = stale0;
+            return flush_post(pf);
+        }
         FireGuard g{0, o_cap, (int64_t)f.nwin, rows_reset_pending ? 1 : 0};
         rows_reset_pending = false;  // the guard zeroes the cursor
         HIPCHECK(launch_fire_guard(d_st, g, stream));
@@ -5053,9 +5110,9 @@ int gw_kernel_time_ms(gw_handle* h, int which, double* ms, int64_t* launches) {
     }
     hipStreamSynchronize(h->stream);
     if (h->sess) return session_kernel_time(h->sess, which, ms, launches);
-    if (which == 3) {
+    if (which >= 3 && which <= 5) {
         if (ms) *ms = 0.0;
-        if (launches) *launches = h->fast_fires;
+        if (launches) *launches = which == 3 ? h->fast_fires : which == 4 ? h->fused_fires : h->fused_revoked;
         return GW_OK;
     }
     KernelTimer& t = which == 0 ? h->t_ingest : which == 1 ? h->t_fire : h->t_apply;

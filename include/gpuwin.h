@@ -385,7 +385,11 @@ void* gw_stream(gw_handle* h);
  * measured with HIP events on the handle's stream.  which: 0 = ingest (per batch;
  * region path: pass 1), 1 = fire, 2 = region pass 2 + apply (per buffer flush).
  * which = 3: *launches = the fires enqueued right behind their flush, without a host
- * round trip between them (gw_advance_watermark's common case), *ms = 0. */
+ * round trip between them (gw_advance_watermark's common case), *ms = 0.
+ * which = 4: *launches = those of them whose rows the flush's apply kernel emitted itself (the
+ * fused fire: its time is part of which = 2, and which = 1 counts no launch for it), *ms = 0.
+ * which = 5: *launches = the fused fires that were revoked (their rows dropped, the windows
+ * fired the exact way instead), *ms = 0. */
 int  gw_kernel_time_ms(gw_handle* h, int which, double* ms, int64_t* launches);
 /* enable: 0 off, 1 every launch, k > 1: the region path's pass 1 (one launch per batch, all
  * alike) is timed on every k-th batch only (two event records per timed launch cost host
