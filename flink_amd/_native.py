@@ -20,6 +20,7 @@ ERRORS = {
 GW_E_INVALID, GW_E_UNSUPPORTED, GW_E_DEVICE, GW_E_OOM, GW_E_OUTPUT_FULL = -1, -2, -3, -4, -5
 GW_E_NO_TIMESTAMP, GW_E_RANGE, GW_E_STATE = -6, -7, -8
 STAGE_VALUE, STAGE_KEY_HASH = 1, 2
+TOPN_MAX_N, TOPN_MAX_WINDOWS, TOPN_SMALLEST, TOPN_F64 = 64, 1024, 1, 2  # gpuwin.h GW_TOPN_*
 
 ASSIGNERS = {"tumbling": 0, "sliding": 1, "session": 2, "count_tumbling": 3, "count_sliding": 4}
 TRIGGERS = {"event_time": 0, "purging_event_time": 1}
@@ -56,7 +57,7 @@ EXPORTS = [
     "gw_ingest_payload", "gw_ingest_payload_device", "gw_drain_payload",
     "gw_snapshot_keys", "gw_snapshot_remap_keys", "gw_snapshot_payloads", "gw_snapshot_remap_payloads",
     "gw_pack_geom_init", "gw_pack_records", "gw_unpack_records", "gw_partition_packed_device", "gw_partition_regions_device", "gw_unpack_device",
-    "gw_select_lookup_device",
+    "gw_select_lookup_device", "gw_top_n_device", "gw_top_n_rows", "gw_top_n_host",
     "gw_exchange_enable_packing", "gw_exchange_last_packed", "gw_exchange_plan_packed",
     "gw_exchange_set_unpack", "gw_exchange_last_words", "gw_ingest_packed_device",
 ]
@@ -219,6 +220,9 @@ def lib() -> ctypes.CDLL:
                                                 p, p, p, p]),
         "gw_unpack_device": (c_int, [i64, p, ctypes.POINTER(GwPackGeom), p, p, p, p]),
         "gw_select_lookup_device": (c_int, [i64, p, i64, p, p, i64, p, p, p, ctypes.POINTER(ctypes.c_int64), p]),
+        "gw_top_n_device": (c_int, [i64, p, p, p, p, i32, i32, p, p, p, p, p, i64, P64, p]),
+        "gw_top_n_rows": (c_int, [p, i32, i32, p, p, p, p, p, i64, P64]),
+        "gw_top_n_host": (c_int, [i64, p, p, p, p, i32, i32, p, p, p, p, p, i64, P64]),
         "gw_exchange_enable_packing": (c_int, [p, i64, i64, i64, i32]),
         "gw_exchange_last_packed": (i64, [p]),
         "gw_exchange_plan_packed": (c_int, [i32, p, p, p, p, p, p, P64, P64]),

@@ -17,6 +17,8 @@
 // hits, each as one contiguous block per region (loaded into LDS and written back whole
 // by k_rgn_apply), and a fire pass streams every array coalesced.
 #pragma once
+#include <string>
+
 #include "gw_device.h"
 
 namespace gw {
@@ -431,6 +433,13 @@ hipError_t launch_select_lookup(int64_t n, const int64_t* sel, int64_t want, con
 size_t select_lookup_scratch_bytes(int64_t n);
 hipError_t launch_unpack(int64_t n, const uint64_t* w, const PackGeom& g, int64_t* key, int64_t* ts, int64_t* val,
                          hipStream_t s);
+// gw_topn.hip: per-window top-N over n > 0 device rows (the contract of gpuwin.h's top-N entry
+// points; arguments already checked).  Waits on s.  host_out: the output columns are host arrays.
+// Windows one selection pass ranks; more take one pass per chunk of this many.
+constexpr int kTopnPassWindows = 16;
+int top_n_run(int64_t n, const int64_t* d_key, const int64_t* d_start, const int64_t* d_end, const int64_t* d_res,
+              int top, int mode, int64_t* key_out, int64_t* start_out, int64_t* end_out, int64_t* res_out,
+              int64_t* rows_out, int64_t cap, int64_t* n_out, bool host_out, hipStream_t s, std::string& why);
 
 // Key -> Java hashCode of the keys a handle was fed with a key_hash column (String,
 // Integer, ... keys mapped to int64 ids by the caller).  The heap backend files a key's

@@ -5274,6 +5274,122 @@ int gw_select_lookup_device(int64_t n, const int64_t* d_sel, int64_t sel_value, 
     return GW_OK;
 }
 
+static int top_n_args(int64_t n, int32_t top, int32_t mode, int32_t allowed, int64_t cap, const int64_t* n_out) {
+    if (!n_out || n < 0 || cap < 0 || (mode & ~allowed)) { g_create_error = "top-N: bad argument"; return GW_E_INVALID; }
+    if (top < 1 || top > GW_TOPN_MAX_N) { g_create_error = "top-N: top outside [1, GW_TOPN_MAX_N]"; return GW_E_INVALID; }
+    return GW_OK;
+}
+
+int gw_top_n_device(int64_t n, const int64_t* d_key, const int64_t* d_start, const int64_t* d_end,
+                    const void* d_result, int32_t top, int32_t mode, int64_t* d_key_out, int64_t* d_start_out,
+                    int64_t* d_end_out, void* d_result_out, int64_t* d_win_rows_out, int64_t cap, int64_t* n_out,
+                    void* stream) {
+    int rc = top_n_args(n, top, mode, GW_TOPN_SMALLEST | GW_TOPN_F64, cap, n_out);
+    if (rc) return rc;
+    *n_out = 0;
+    if (n == 0) return GW_OK;
+    if (!d_key || !d_start || !d_end || !d_result || (cap > 0 && (!d_key_out || !d_start_out || !d_end_out || !d_result_out))) {
+        g_create_error = "top-N: null column";
+        return GW_E_INVALID;
+    }
+    std::string why;
+    rc = top_n_run(n, d_key, d_start, d_end, (const int64_t*)d_result, top, mode, d_key_out, d_start_out, d_end_out,
+                   (int64_t*)d_result_out, d_win_rows_out, cap, n_out, false, (hipStream_t)stream, why);
+    if (rc) g_create_error = why;
+    return rc;
+}
+
+int gw_top_n_rows(gw_handle* h, int32_t top, int32_t mode, int64_t* key, int64_t* start, int64_t* end, void* result,
+                  int64_t* win_rows, int64_t cap, int64_t* n) {
+    if (!h) return GW_E_INVALID;
+    if (h->failed) return GW_E_STATE;
+    if (!n || cap < 0 || (mode & ~GW_TOPN_SMALLEST)) return h->fail(GW_E_INVALID, "gw_top_n_rows: bad argument");
+    if (top < 1 || top > GW_TOPN_MAX_N) return h->fail(GW_E_INVALID, "gw_top_n_rows: top outside [1, %d]", GW_TOPN_MAX_N);
+    if (h->session || h->cfg.assigner == GW_SESSION || h->cfg.assigner == GW_COUNT_TUMBLING ||
+        h->cfg.assigner == GW_COUNT_SLIDING)
+        return h->fail(GW_E_UNSUPPORTED, "gw_top_n_rows: session and count windows are per key");
+    hipSetDevice(h->cfg.device);
+    *n = 0;
+    const int64_t *dk, *ds, *de;
+    const void* dr;
+    int64_t pending = 0;
+    int rc = gw_rows_device(h, &dk, &ds, &de, &dr, &pending);
+    if (rc) return rc;
+    if (pending == 0) return GW_OK;
+    if (cap > 0 && (!key || !start || !end || !result)) return h->fail(GW_E_INVALID, "gw_top_n_rows: null column");
+    if (result_is_double(h->cfg.agg)) mode |= GW_TOPN_F64;
+    std::string why;
+    rc = top_n_run(pending, dk, ds, de, (const int64_t*)dr, top, mode, key, start, end, (int64_t*)result, win_rows, cap,
+                   n, true, h->stream, why);
+    if (rc) return h->fail(rc, "%s", why.c_str());
+    return GW_OK;
+}
+
+int gw_top_n_host(int64_t n, const int64_t* key, const int64_t* start, const int64_t* end, const void* result,
+                  int32_t top, int32_t mode, int64_t* key_out, int64_t* start_out, int64_t* end_out, void* result_out,
+                  int64_t* win_rows_out, int64_t cap, int64_t* n_out) {
+    int rc = top_n_args(n, top, mode, GW_TOPN_SMALLEST | GW_TOPN_F64, cap, n_out);
+    if (rc) return rc;
+    *n_out = 0;
+    if (n == 0) return GW_OK;
+    if (!key || !start || !end || !result || (cap > 0 && (!key_out || !start_out || !end_out || !result_out))) {
+        g_create_error = "top-N: null column";
+        return GW_E_INVALID;
+    }
+    try {
+        const int64_t* res = (const int64_t*)result;
+        auto order = [&](int64_t bits) {
+            const int64_t o = (mode & GW_TOPN_F64) ? f64_order_key(bits) : bits;
+            return (mode & GW_TOPN_SMALLEST) ? ~o : o;  // the complement reverses the signed order
+        };
+        // rows by (end, order word descending, key ascending)
+        std::vector<int64_t> idx((size_t)n);
+        for (int64_t i = 0; i < n; ++i) idx[i] = i;
+        std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) {
+            if (end[a] != end[b]) return end[a] < end[b];
+            const int64_t oa = order(res[a]), ob = order(res[b]);
+            if (oa != ob) return oa > ob;
+            if (key[a] != key[b]) return key[a] < key[b];
+            return a < b;
+        });
+        int64_t windows = 0, total = 0;
+        for (int64_t i = 0; i < n;) {
+            int64_t j = i;
+            for (; j < n && end[idx[j]] == end[idx[i]]; ++j)
+                if (start[idx[j]] != start[idx[i]]) {
+                    g_create_error = "top-N: rows of one window end carry different starts";
+                    return GW_E_INVALID;
+                }
+            if (++windows > GW_TOPN_MAX_WINDOWS) {
+                g_create_error = "top-N: more than GW_TOPN_MAX_WINDOWS distinct window ends in one call";
+                return GW_E_UNSUPPORTED;
+            }
+            total += std::min<int64_t>(top, j - i);
+            i = j;
+        }
+        *n_out = total;
+        if (total > cap) { g_create_error = "top-N: output arrays too small"; return GW_E_OUTPUT_FULL; }
+        int64_t o = 0;
+        for (int64_t i = 0; i < n;) {
+            int64_t j = i;
+            while (j < n && end[idx[j]] == end[idx[i]]) ++j;
+            for (int64_t r = i; r < j && r < i + top; ++r, ++o) {
+                const int64_t x = idx[r];
+                key_out[o] = key[x];
+                start_out[o] = start[x];
+                end_out[o] = end[x];
+                ((int64_t*)result_out)[o] = res[x];
+                if (win_rows_out) win_rows_out[o] = j - i;
+            }
+            i = j;
+        }
+    } catch (const std::bad_alloc&) {
+        g_create_error = "top-N: out of host memory";
+        return GW_E_OOM;
+    }
+    return GW_OK;
+}
+
 int gw_unpack_device(int64_t n, const uint64_t* d_words, const gw_pack_geom* g, int64_t* d_key, int64_t* d_ts,
                      int64_t* d_value, void* stream) {
     if (n < 0 || !g || !g->enabled || g->pane <= 0 || (n > 0 && (!d_words || !d_key || !d_ts))) return GW_E_INVALID;

@@ -247,6 +247,66 @@ def select_lookup_device(sel, sel_value: int, idx, dictionary, ts, key_out, ts_o
     return int(n_out.value)
 
 
+def _top_n_mode(smallest: bool, f64: bool) -> int:
+    return (N.TOPN_SMALLEST if smallest else 0) | (N.TOPN_F64 if f64 else 0)
+
+
+def top_n_device(key, start, end, result, top: int, smallest: bool = False, f64: bool = False, stream=None):
+    """gw_top_n_device over torch device tensors (8-byte columns of n rows in any order): per
+    window (rows sharing `end`) the `top` rows with the largest result (smallest=True: the
+    smallest; f64=True: result bits are doubles in Double.compare order), ties to the smaller key,
+    windows in ascending end, best first.  Returns device tensors (key, start, end, result,
+    win_rows); result has the dtype it came in.  The windowAll top-N stage of Nexmark Q5 / Q7
+    behind the keyed window aggregate.  Waits on `stream` (default: torch's current)."""
+    import torch
+    n = key.numel()
+    if stream is None:
+        stream = torch.cuda.current_stream(key.device).cuda_stream
+    mode = _top_n_mode(smallest, f64)
+    n_out = ctypes.c_int64(0)
+    cap = min(n, 4096)  # top * windows at most; a retry with the needed size when it is more
+    while True:
+        out = [torch.empty(cap, dtype=torch.int64, device=key.device) for _ in range(5)]
+        rc = N.lib().gw_top_n_device(n, key.data_ptr(), start.data_ptr(), end.data_ptr(), result.data_ptr(), int(top),
+                                     mode, *[o.data_ptr() for o in out], cap, ctypes.byref(n_out),
+                                     ctypes.c_void_p(stream) if stream else None)
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    k, s, e, r, w = (o[:n_out.value] for o in out)
+    return k, s, e, r.view(result.dtype), w
+
+
+def top_n_host(key, start, end, result, top: int, smallest: bool = False, f64: bool = False):
+    """gw_top_n_host over numpy columns: the contract of top_n_device as pure host code.  A job
+    at parallelism > 1 combines its subtasks' top-N lists with it (the keys are partitioned, so
+    the top-N of the concatenated lists is the global one).  result: int64 or float64 (f64
+    follows from a float64 dtype)."""
+    key, start, end = (np.ascontiguousarray(x, dtype=np.int64) for x in (key, start, end))
+    result = np.ascontiguousarray(result)
+    is_f = result.dtype == np.float64
+    bits = result.view(np.int64) if is_f else result.astype(np.int64, copy=False)
+    n = len(key)
+    if not (len(start) == len(end) == len(bits) == n):
+        raise ValueError("column lengths differ")
+    mode = _top_n_mode(smallest, f64 or is_f)
+    n_out = ctypes.c_int64(0)
+    cap = min(n, 4096)
+    while True:
+        out = [np.empty(cap, np.int64) for _ in range(5)]
+        rc = N.lib().gw_top_n_host(n, _ptr(key), _ptr(start), _ptr(end), _ptr(bits), int(top), mode,
+                                   *[_ptr(o) for o in out], cap, ctypes.byref(n_out))
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    k, s, e, r, w = (o[:n_out.value] for o in out)
+    return k, s, e, (r.view(np.float64) if is_f else r), w
+
+
 # ------------------------------------------------------------------------ operator
 class GpuWindowOperator:
     """Keyed event-time window operator on one MI355X (one Flink subtask).
@@ -742,6 +802,28 @@ class GpuWindowOperator:
             return
         N.check(N.lib().gw_clear_rows(self._h), self._h)
 
+    def top_n_rows(self, top: int, smallest: bool = False):
+        """Per window, the `top` pending rows with the largest (smallest=True: smallest) result,
+        ties to the smaller key, ranked on the device (gw_top_n_rows): numpy (key, start, end,
+        result, win_rows), windows in ascending end, best first; win_rows = the pending rows of
+        the row's window.  The rows stay pending: follow with clear_rows() or drain().  The
+        non-keyed top-N stage of Nexmark Q5 / Q7 without draining one row per key."""
+        if self._deferred:
+            return tuple(np.empty(0, np.float64 if (self.is_double_out and i == 3) else np.int64) for i in range(5))
+        mode = N.TOPN_SMALLEST if smallest else 0
+        n = ctypes.c_int64(0)
+        cap = 4096
+        while True:
+            out = [np.empty(cap, np.int64) for _ in range(5)]
+            rc = N.lib().gw_top_n_rows(self._h, int(top), mode, *[_ptr(o) for o in out], cap, ctypes.byref(n))
+            if rc == N.GW_E_OUTPUT_FULL and n.value > cap:
+                cap = n.value
+                continue
+            N.check(rc, self._h)
+            break
+        k, s, e, r, w = (o[:n.value] for o in out)
+        return k, s, e, (r.view(np.float64) if self.is_double_out else r), w
+
     def rows_device(self):
         p = [ctypes.c_void_p() for _ in range(4)]
         n = ctypes.c_int64(0)
@@ -880,6 +962,52 @@ class DataStreamResult:
                     self.op.process_element(el)
             self.op.end_input()
             out = [r for r in self.op.get_output() if isinstance(r, StreamRecord)]
+        return out
+
+    def window_all_top_n(self, n: int, smallest: bool = False) -> "WindowAllTopN":
+        """...aggregate(...) followed by a windowAll per-window top-N (Nexmark Q5's "hot items",
+        Q7's highest bid): per fired window the n rows with the largest (smallest) result."""
+        return WindowAllTopN(self, n, smallest)
+
+    windowAllTopN = window_all_top_n
+
+
+class WindowAllTopN:
+    """keyBy().window().aggregate(...) -> windowAll top-N in one call: at every watermark the
+    fired rows are ranked on the device (GpuWindowOperator.top_n_rows) and only the winners come
+    to the host, as the StreamRecords the operator emits for a fired row ((key, start, end,
+    result), timestamp end - 1), windows in ascending end, best first."""
+
+    def __init__(self, result: DataStreamResult, n: int, smallest: bool = False):
+        op = result.op
+        if op._payload or op.window_function is not None:
+            raise ValueError("window_all_top_n ranks plain aggregate rows (no minBy / first-element / window function)")
+        if not 1 <= n <= N.TOPN_MAX_N:
+            raise ValueError(f"top-N size must be in [1, {N.TOPN_MAX_N}]")
+        self.result, self.n, self.smallest = result, n, smallest
+
+    def execute_and_collect(self) -> list:
+        op = self.result.op
+        out = []
+
+        def watermark(ts):
+            op._flush()
+            op.advance_watermark(ts)
+            if op.pending_rows() == 0:
+                return
+            k, s, e, r, _ = op.top_n_rows(self.n, self.smallest)
+            op.clear_rows()
+            for i in range(len(k)):
+                end = int(e[i])
+                out.append(StreamRecord((op._decode_key(int(k[i])), int(s[i]), end, r[i]), end - 1))
+
+        with op:
+            for el in self.result.ws.keyed.env.elements:
+                if isinstance(el, Watermark):
+                    watermark(el.timestamp)
+                else:
+                    op.process_element(el)
+            watermark(MAX_WATERMARK.timestamp)  # BoundedOneInput.endInput
         return out
 
 

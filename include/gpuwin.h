@@ -367,6 +367,56 @@ int  gw_rows_device(gw_handle* h, const int64_t** d_key, const int64_t** d_start
 /* Drop all pending rows (after a device consumer read them). */
 int  gw_clear_rows(gw_handle* h);
 
+/* ---- per-window top-N over fired rows ----------------------------------------
+ * The non-keyed stage that follows the keyed window aggregate in Nexmark Q5 ("hot items": per
+ * window, the auctions with the highest count) and Q7 (per-window maximum): in Flink a
+ * windowAll(...).maxBy(...) or a top-N process function over the keyed stage's output.  Run on
+ * the device it leaves `top` rows per window to bring to the host instead of one per live key.
+ *
+ * Input: n rows in the columns key, start, end (int64) and result (8 bytes), in any order, rows
+ * of different windows interleaved.  A window is identified by its end; every row with the same
+ * end must carry the same start (GW_E_INVALID otherwise), which holds for the rows of any
+ * tumbling or sliding handle, window classes included (the size is fixed).
+ * Order of result: signed int64; with GW_TOPN_F64 that of Double.compare (-0.0 < 0.0, every NaN
+ * equal to every other and greater than +inf).  The best rows are the largest, with
+ * GW_TOPN_SMALLEST the smallest.  Among equal results the smaller key (signed) wins: Flink's
+ * maxBy keeps the first of equal elements in arrival order, but behind a parallel upstream that
+ * order is undefined, so the key decides and the answer is reproducible.
+ * Output: windows in ascending end, within a window up to `top` rows, best first, as key, start,
+ * end, result and (win_rows, may be NULL) the number of input rows of the row's window;
+ * *n_out = the sum over windows of min(top, rows of the window).  result bits come back as
+ * they went in, except that a NaN may come back as the canonical NaN.
+ * Limits: 1 <= top <= GW_TOPN_MAX_N (GW_E_INVALID); at most GW_TOPN_MAX_WINDOWS distinct ends
+ * per call (GW_E_UNSUPPORTED); outputs of cap < *n_out rows: GW_E_OUTPUT_FULL with the needed
+ * number in *n_out.  n = 0: GW_OK and no rows.
+ *
+ * gw_top_n_device: stateless, device columns in and out; waits on `stream` (the result size is
+ * known only then), using scratch of its own per device.  Errors: gw_last_error of NULL.
+ * gw_top_n_rows: over the handle's pending rows (the view gw_rows_device gives: plain,
+ * window-class, first-element and minBy handles) on the handle's stream, into host arrays.
+ * GW_TOPN_F64 follows from the handle's aggregate; mode carries GW_TOPN_SMALLEST only.  The rows
+ * stay pending: follow it with gw_clear_rows or gw_drain.  It ranks whatever is pending: under
+ * allowed lateness that may include the re-fired rows of a window next to its earlier ones
+ * (drain or clear at every watermark to rank one firing at a time).  Session and count-window
+ * handles: GW_E_UNSUPPORTED (their windows are per key).
+ * gw_top_n_host: the same contract as pure host code (no device, no handle): how a job at
+ * parallelism > 1 combines its subtasks' lists.  Key groups partition the keys over the
+ * subtasks, so the top-N of the concatenated per-subtask top-Ns is the global top-N, and
+ * top x windows rows per subtask need no collective of their own. */
+#define GW_TOPN_MAX_N       64
+#define GW_TOPN_MAX_WINDOWS 1024
+#define GW_TOPN_SMALLEST    1
+#define GW_TOPN_F64         2
+int  gw_top_n_device(int64_t n, const int64_t* d_key, const int64_t* d_start, const int64_t* d_end,
+                     const void* d_result, int32_t top, int32_t mode, int64_t* d_key_out, int64_t* d_start_out,
+                     int64_t* d_end_out, void* d_result_out, int64_t* d_win_rows_out, int64_t cap, int64_t* n_out,
+                     void* stream);
+int  gw_top_n_rows(gw_handle* h, int32_t top, int32_t mode, int64_t* key, int64_t* start, int64_t* end,
+                   void* result, int64_t* win_rows, int64_t cap, int64_t* n);
+int  gw_top_n_host(int64_t n, const int64_t* key, const int64_t* start, const int64_t* end, const void* result,
+                   int32_t top, int32_t mode, int64_t* key_out, int64_t* start_out, int64_t* end_out,
+                   void* result_out, int64_t* win_rows_out, int64_t cap, int64_t* n_out);
+
 int64_t gw_late_dropped(const gw_handle* h);
 /* Late-data side output (GW_FLAG_LATE_SIDE_OUTPUT; WindowedStream.sideOutputLateData, RS/api/
  * datastream/WindowedStream.java): the records WindowOperator.processElement skips as late
