@@ -28,6 +28,7 @@
 #include "gw_kernels.h"
 #include "gw_netbuf.h"
 #include "gw_session.h"
+#include "gw_snapshot.h"
 #include "gw_sort.h"
 
 using namespace gw;
@@ -37,9 +38,6 @@ namespace {
 thread_local std::string g_create_error;
 
 constexpr int64_t kMaxIngest = (int64_t)1 << 30;
-constexpr uint32_t kSnapMaxVersion = 4;  // gw_handle::SnapHeader versions
-constexpr int64_t kSnapKeyHashes = 1;    // SnapHeader::flags
-constexpr int64_t kSnapFirstElement = 2; // SnapHeader::flags: v4 entries end with the first element's payload
 
 // Host-time profile of the ingest path (GW_HOST_PROFILE=1: printed by gw_destroy).
 struct HostProf {
@@ -1821,22 +1819,8 @@ struct gw_handle {
     }
 
     // ---------------------------------------------------------------- snapshot
-    // Blob (little-endian): SnapHeader, int64 kg_offsets[kg_hi - kg_lo + 2], then the entries
-    // of each key group.  Versions: 2 session windows, 3 count windows (fixed-size entries of
-    // `reserved` int64 words, offsets in entries), 4 tumbling / sliding windows (the heap
-    // backend's per-key-group byte layout, offsets in bytes; see snapshot_heap).
-    // flags: kSnapKeyHashes -- the keys came with a key_hash column (String, Integer, ...
-    // keys as caller ids): each state entry carries the key's Java hashCode after the key
-    // (version 4: be32 after the be64 key; versions 2 / 3: one more int64 word at the end).
-    struct SnapHeader {
-        char magic[4];
-        uint32_t version;
-        int32_t agg, assigner;
-        int64_t size, slide, offset, gap, flags;
-        int32_t max_parallelism, kg_lo, kg_hi, reserved;
-        int64_t fired_lo, fired_hi;
-        int64_t entries;  // entries (versions 2, 3) / payload bytes (version 4)
-    };
+    // The blob format, its bounds-checked readers and its writer: gw_snapshot.h (gw::snap).
+    // Here: what needs the handle -- device collection, accumulators, key hashes, the overlay.
 
     // -------------------------------------------- restored window state (the overlay)
     // A heap-layout blob holds the reference's state per (key, window) and its timers.
@@ -1950,41 +1934,58 @@ struct gw_handle {
     // Accumulator <-> cell words (the serializer's value, gw_common.h cells).
     void acc_to_be(std::vector<uint8_t>& o, int64_t a0, int64_t a1) const {
         switch (cfg.agg) {
-        case GW_SUM_I32: be32(o, (int32_t)(uint32_t)(uint64_t)a0); break;
-        case GW_MIN_F64: case GW_MAX_F64: be64(o, f64_from_order_key(a0)); break;
-        case GW_AVG_I64: case GW_AVG_F64: be64(o, a0); be64(o, a1); break;
-        default: be64(o, a0); break;
+        case GW_SUM_I32: snap::put32(o, (int32_t)(uint32_t)(uint64_t)a0); break;
+        case GW_MIN_F64: case GW_MAX_F64: snap::put64(o, f64_from_order_key(a0)); break;
+        case GW_AVG_I64: case GW_AVG_F64: snap::put64(o, a0); snap::put64(o, a1); break;
+        default: snap::put64(o, a0); break;
         }
-    }
-    int acc_bytes() const {
-        return cfg.agg == GW_SUM_I32 ? 4 : (cfg.agg == GW_AVG_I64 || cfg.agg == GW_AVG_F64) ? 16 : 8;
     }
     void acc_from_be(const uint8_t* p, int64_t& a0, int64_t& a1) const {
         a1 = 0;
         switch (cfg.agg) {
-        case GW_SUM_I32: a0 = (int64_t)rd32(p); break;
-        case GW_MIN_F64: case GW_MAX_F64: a0 = f64_order_key(rd64(p)); break;
-        case GW_AVG_I64: case GW_AVG_F64: a0 = rd64(p); a1 = rd64(p + 8); break;
-        default: a0 = rd64(p); break;
+        case GW_SUM_I32: a0 = (int64_t)snap::get32(p); break;
+        case GW_MIN_F64: case GW_MAX_F64: a0 = f64_order_key(snap::get64(p)); break;
+        case GW_AVG_I64: case GW_AVG_F64: a0 = snap::get64(p); a1 = snap::get64(p + 8); break;
+        default: a0 = snap::get64(p); break;
         }
     }
-    static void be64(std::vector<uint8_t>& o, int64_t v) {
-        for (int i = 0; i < 8; ++i) o.push_back((uint8_t)((uint64_t)v >> (56 - 8 * i)));
-    }
-    static void be32(std::vector<uint8_t>& o, int32_t v) {
-        for (int i = 0; i < 4; ++i) o.push_back((uint8_t)((uint32_t)v >> (24 - 8 * i)));
-    }
-    static int64_t rd64(const uint8_t* p) {
-        uint64_t v = 0;
-        for (int i = 0; i < 8; ++i) v = (v << 8) | p[i];
-        return (int64_t)v;
-    }
-    static int32_t rd32(const uint8_t* p) {
-        uint32_t v = 0;
-        for (int i = 0; i < 4; ++i) v = (v << 8) | p[i];
-        return (int32_t)v;
-    }
     i128 win_start(i128 k) const { return (i128)cfg.offset + k * (i128)slide(); }
+
+    int fail(const snap::Err& e) { return fail(e.code, "%s", e.reason); }
+    // The header of this handle's blobs.
+    snap::Header blob_header(uint32_t version, int32_t kg_lo, int32_t kg_hi, bool hashed) const {
+        snap::Header hd{};
+        hd.version = version;
+        hd.agg = cfg.agg; hd.assigner = cfg.assigner;
+        hd.size = cfg.size; hd.slide = cfg.slide; hd.offset = cfg.offset; hd.gap = cfg.gap;
+        hd.flags = hashed ? snap::kKeyHashes : 0;
+        hd.max_parallelism = cfg.max_parallelism; hd.kg_lo = kg_lo; hd.kg_hi = kg_hi;
+        return hd;
+    }
+    int finish_blob(snap::Writer& w, const snap::Header& hd, void* buf, int64_t cap, int64_t* len) {
+        if (w.finish(hd, buf, cap, len)) return fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)*len);
+        return GW_OK;
+    }
+    // A window-layout state entry.
+    void put_state(std::vector<uint8_t>& st, int64_t s0, int64_t e0, int64_t key, const KhmHost& kh, int64_t a0,
+                   int64_t a1) const {
+        snap::put64(st, s0); snap::put64(st, e0); snap::put64(st, key);
+        if (kh.on()) snap::put32(st, kh.hash(key));
+        acc_to_be(st, a0, a1);
+    }
+    // A window's trigger timer (while it has not fired) and, under allowed lateness, its
+    // cleanup timer (registerCleanupTimer :631-643; with lateness 0 the two coincide).
+    void put_window_timers(std::vector<uint8_t>& tm, int32_t& ntm, bool trigger, int64_t key, int64_t s0, int64_t e0) const {
+        const i128 mx = (i128)e0 - 1, ct = mx + (i128)cfg.allowed_lateness;
+        if (trigger) {
+            snap::put_timer(tm, (int64_t)mx, key, s0, e0);
+            ntm++;
+        }
+        if (cfg.allowed_lateness > 0 && ct < (i128)INT64_MAX) {
+            snap::put_timer(tm, (int64_t)ct, key, s0, e0);
+            ntm++;
+        }
+    }
 
     // Heap-layout snapshot (version 4) of the tumbling / sliding window state: per key group,
     // the reference's "window-contents" entries (window, key, accumulator) -- every (key,
@@ -2079,12 +2080,10 @@ struct gw_handle {
         for (size_t i = 0; i < kgs.size(); ++i) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
         std::vector<std::vector<OvEntry>> ov_kg(nk);
         for (auto& e : ov) ov_kg[kg_of(e.key) - kg_lo].push_back(e);
-        std::vector<uint8_t> pay;
-        std::vector<int64_t> offs(nk + 1, 0);
+        snap::Writer w;
         const int64_t id0 = identity0(cfg.agg);
-        const i128 LMAX = INT64_MAX;
         for (int g = 0; g < nk; ++g) {
-            offs[g] = (int64_t)pay.size();
+            w.begin_group();
             auto& ix = by_kg[g];
             std::sort(ix.begin(), ix.end(), [&](int64_t x, int64_t y) {
                 return col[0][x] != col[0][y] ? col[0][x] < col[0][y] : col[1][x] < col[1][y];
@@ -2142,48 +2141,18 @@ struct gw_handle {
                     if (!any) continue;
                     const i128 s0 = win_start(k), e0 = s0 + (i128)size();
                     if (!fits64(s0) || !fits64(e0)) return fail(GW_E_RANGE, "window bounds overflow int64");
-                    be64(st, (int64_t)s0); be64(st, (int64_t)e0); be64(st, key);
-                    if (hashed) be32(st, kh.hash(key));
-                    acc_to_be(st, r0, r1);
+                    put_state(st, (int64_t)s0, (int64_t)e0, key, kh, r0, r1);
                     nst++;
-                    const i128 mx = e0 - 1;
-                    if (timer) {
-                        be64(tm, (int64_t)((uint64_t)(int64_t)mx ^ 0x8000000000000000ull));
-                        be64(tm, key); be64(tm, (int64_t)s0); be64(tm, (int64_t)e0);
-                        ntm++;
-                    }
-                    const i128 ct = mx + (i128)cfg.allowed_lateness;
-                    if (lat && ct < LMAX) {
-                        be64(tm, (int64_t)((uint64_t)(int64_t)ct ^ 0x8000000000000000ull));
-                        be64(tm, key); be64(tm, (int64_t)s0); be64(tm, (int64_t)e0);
-                        ntm++;
-                    }
+                    put_window_timers(tm, ntm, timer, key, (int64_t)s0, (int64_t)e0);
                 }
             }
-            be32(pay, nst);
-            pay.insert(pay.end(), st.begin(), st.end());
-            be32(pay, 0);  // merging window set: none for tumbling / sliding windows
-            be32(pay, ntm);
-            pay.insert(pay.end(), tm.begin(), tm.end());
+            w.section(nst, st);
+            w.section(0, {});  // merging window set: none for tumbling / sliding windows
+            w.section(ntm, tm);
         }
-        offs[nk] = (int64_t)pay.size();
-        const int64_t need = (int64_t)sizeof(SnapHeader) + (int64_t)(nk + 1) * 8 + (int64_t)pay.size();
-        *len = need;
-        if (!buf) return GW_OK;
-        if (cap < need) return fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)need);
-        SnapHeader hd{};
-        memcpy(hd.magic, "GWS1", 4);
-        hd.version = 4;
-        hd.agg = cfg.agg; hd.assigner = cfg.assigner;
-        hd.size = cfg.size; hd.slide = slide(); hd.offset = cfg.offset; hd.gap = cfg.gap;
-        hd.flags = hashed ? kSnapKeyHashes : 0;
-        hd.max_parallelism = cfg.max_parallelism; hd.kg_lo = kg_lo; hd.kg_hi = kg_hi;
-        hd.entries = (int64_t)pay.size();
-        char* out = (char*)buf;
-        memcpy(out, &hd, sizeof hd);
-        memcpy(out + sizeof hd, offs.data(), (nk + 1) * 8);
-        if (!pay.empty()) memcpy(out + sizeof hd + (nk + 1) * 8, pay.data(), pay.size());
-        return GW_OK;
+        snap::Header hd = blob_header(4, kg_lo, kg_hi, hashed);
+        hd.slide = slide();
+        return finish_blob(w, hd, buf, cap, len);
     }
 
     // Restore one heap-layout blob (any key-group range; several calls after rescaling).
@@ -2193,69 +2162,61 @@ struct gw_handle {
     // blob leaves the handle as it was; `dry` stops there (composite handles check every
     // class's part before restoring any).
     int restore_heap(const void* buf, int64_t len, bool dry = false) {
-        if (!buf || len < (int64_t)sizeof(SnapHeader)) return fail(GW_E_INVALID, "snapshot blob too short");
-        SnapHeader hd;
-        memcpy(&hd, buf, sizeof hd);
-        if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version < 1 || hd.version > kSnapMaxVersion)
-            return fail(GW_E_INVALID, "not a gpuwin snapshot");
+        snap::Header hd;
+        snap::Cursor c;
+        snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
+        if (e) return fail(e);
         if (hd.version != 4 || hd.agg != cfg.agg || hd.assigner != cfg.assigner || hd.size != cfg.size ||
             hd.slide != slide() || hd.offset != cfg.offset || hd.max_parallelism != cfg.max_parallelism)
             return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
         if (stats.events_in != 0 || wm != INT64_MIN)
             return fail(GW_E_STATE, "restore after processing started (initializeState runs before the first record)");
-        const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-        const int64_t pay0 = (int64_t)sizeof hd + (nk + 1) * 8;
-        if (nk <= 0 || hd.entries < 0 || len < pay0 || hd.entries > len - pay0) return fail(GW_E_INVALID, "truncated snapshot blob");
-        const uint8_t* p = (const uint8_t*)buf + pay0;
-        const uint8_t* end = p + hd.entries;
-        const int ab = acc_bytes();
-        const int hb = (hd.flags & kSnapKeyHashes) ? 4 : 0;
+        if ((e = snap::payload(buf, len, hd, c))) return fail(e);
+        hd.flags &= snap::kKeyHashes;  // entries of this handle's width, whatever else the blob claims
+        const bool hashed = hd.flags != 0;
+        const int64_t acc_at = snap::state_acc_at(hd);
         std::vector<OvEntry> pend;  // the blob's entries, appended to ov_pending once all is checked
         std::vector<int64_t> hkeys;  // (key, hash) of a hashed blob's entries
         std::vector<int32_t> hvals;
+        std::vector<const uint8_t*> timers;  // of the current key group
+        size_t base = 0;                     // its first entry in pend
         auto by_key_k = [](const OvEntry& x, const OvEntry& y) { return x.key != y.key ? x.key < y.key : x.k < y.k; };
-#define NEED(x) do { if ((x) < 0 || (int64_t)(x) > end - p) return fail(GW_E_INVALID, "truncated snapshot blob"); } while (0)
-        for (int64_t g = 0; g < nk; ++g) {
-            NEED(4);
-            const int32_t ns = rd32(p); p += 4;
-            if (ns < 0) return fail(GW_E_INVALID, "negative entry count in snapshot key group");
-            NEED((int64_t)ns * (24 + hb + ab));
-            const size_t base = pend.size();
-            for (int32_t i = 0; i < ns; ++i) {
-                const int64_t s0 = rd64(p), e0 = rd64(p + 8), key = rd64(p + 16);
-                const i128 k = floor_div((i128)s0 - cfg.offset, (i128)slide());
-                if (win_start(k) != (i128)s0 || (i128)s0 + size() != (i128)e0)
-                    return fail(GW_E_INVALID, "snapshot window [%lld, %lld) is not a window of this assigner",
-                                (long long)s0, (long long)e0);
-                OvEntry e{key, (int64_t)k, 0, 0, 0};
-                if (hb) {
-                    hkeys.push_back(key);
-                    hvals.push_back(rd32(p + 24));
+        auto win_k = [&](int64_t s0) { return floor_div((i128)s0 - cfg.offset, (i128)slide()); };
+        e = snap::walk_windows(
+            hd, c,
+            [&](const uint8_t* p) {
+                const int64_t s0 = snap::state_start(p), e0 = snap::state_end(p), key = snap::state_key(p);
+                const i128 k = win_k(s0);
+                if (win_start(k) != (i128)s0 || (i128)s0 + size() != (i128)e0) {
+                    fail(GW_E_INVALID, "snapshot window [%lld, %lld) is not a window of this assigner", (long long)s0,
+                         (long long)e0);
+                    return snap::invalid(err.c_str());
                 }
-                acc_from_be(p + 24 + hb, e.a0, e.a1);
-                pend.push_back(e);
-                p += 24 + hb + ab;
-            }
-            NEED(4);
-            if (rd32(p) != 0) return fail(GW_E_INVALID, "merging window set in a tumbling / sliding snapshot");
-            p += 4;
-            NEED(4);
-            const int32_t nt = rd32(p); p += 4;
-            if (nt < 0) return fail(GW_E_INVALID, "negative timer count in snapshot key group");
-            NEED((int64_t)nt * 32);
-            // an event-time timer at the window's maxTimestamp: the window has not fired
-            std::sort(pend.begin() + base, pend.end(), by_key_k);
-            for (int32_t i = 0; i < nt; ++i, p += 32) {
-                const int64_t ts = (int64_t)((uint64_t)rd64(p) ^ 0x8000000000000000ull);
-                const int64_t key = rd64(p + 8), s0 = rd64(p + 16), e0 = rd64(p + 24);
-                if (ts != (int64_t)((uint64_t)e0 - 1)) continue;  // cleanup timer: implied by the state
-                const int64_t k = (int64_t)floor_div((i128)s0 - cfg.offset, (i128)slide());
-                auto it = std::lower_bound(pend.begin() + base, pend.end(), OvEntry{key, k, 0, 0, 0}, by_key_k);
-                if (it != pend.end() && it->key == key && it->k == k) it->flags |= kOvTimer;
-            }
-        }
-#undef NEED
-        if (p != end) return fail(GW_E_INVALID, "snapshot blob has trailing bytes");
+                OvEntry o{key, (int64_t)k, 0, 0, 0};
+                if (hashed) {
+                    hkeys.push_back(key);
+                    hvals.push_back(snap::state_hash(p));
+                }
+                acc_from_be(p + acc_at, o.a0, o.a1);
+                pend.push_back(o);
+                return snap::Err{};
+            },
+            snap::NoSets{"merging window set in a tumbling / sliding snapshot"},
+            [&](const uint8_t* t) { timers.push_back(t); },
+            [&] {
+                // an event-time timer at the window's maxTimestamp: the window has not fired
+                std::sort(pend.begin() + base, pend.end(), by_key_k);
+                for (const uint8_t* t : timers) {
+                    // a cleanup timer: implied by the state
+                    if (snap::timer_time(t) != (int64_t)((uint64_t)snap::timer_end(t) - 1)) continue;
+                    const OvEntry want{snap::timer_key(t), (int64_t)win_k(snap::timer_start(t)), 0, 0, 0};
+                    auto it = std::lower_bound(pend.begin() + base, pend.end(), want, by_key_k);
+                    if (it != pend.end() && it->key == want.key && it->k == want.k) it->flags |= kOvTimer;
+                }
+                timers.clear();
+                base = pend.size();
+            });
+        if (e) return fail(e);
         int rc = khm_check_host(hkeys, hvals);
         if (rc || dry) return rc;
         ov_pending.insert(ov_pending.end(), pend.begin(), pend.end());
@@ -2269,27 +2230,28 @@ struct gw_handle {
     // the window contents the evicting operator keeps (EvictingWindowOperator.java:92-135).
     uint32_t slot_blob_version() const { return cfg.assigner == GW_COUNT_SLIDING ? 3u : 4u; }
 
-    // countWindow(size) = GlobalWindows + PurgingTrigger(CountTrigger(size)) (KeyedStream.java:
-    // 676-678) in the heap layout (blob version 4, as oracle/flink_oracle.c count_snapshot):
-    // per key group "window-contents" = be32 n; n x (GlobalWindow = one byte 0, key, [be32
-    // hash,] state) -- the fold of the key's elements since its last FIRE_AND_PURGE, i.e. the
-    // current count pane (a tumbling count window is one pane); "count" = be32 n; n x (byte 0,
-    // key, [be32 hash,] be64 c mod size) -- CountTrigger's ReducingState<Long>
-    // (CountTrigger.java:39-40); be32 0 timers (GlobalWindow ends at Long.MAX_VALUE: no cleanup
-    // timer; CountTrigger registers none).  A key whose element count is a multiple of size
-    // was just purged and holds no state.  The sliding form keeps the version-3 layout.
-    int snapshot_count_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
+    // The slot table's entries of [kg_lo, kg_hi] with their key groups (by the key's own hash
+    // when the keys came with one).
+    int collect_slots(int32_t kg_lo, int32_t kg_hi, KhmHost& kh, std::vector<int64_t>& ent, std::vector<int32_t>& kgs) {
         int rc;
         if ((rc = session_refresh(sess, err))) return fail(rc, "%s", err.c_str());
-        KhmHost kh;
         if ((rc = khm_host(kh))) return rc;
-        const bool hashed = kh.on();
+        std::function<int32_t(int64_t)> hash_of;
+        if (kh.on()) hash_of = [&](int64_t k) { return kh.hash(k); };
+        if ((rc = session_collect(sess, kg_lo, kg_hi, ent, kgs, err, hash_of))) return fail(rc, "%s", err.c_str());
+        return GW_OK;
+    }
+
+    // A tumbling count window in the heap layout (blob version 4, snap::walk_count_windows):
+    // the contents are the current count pane (a tumbling count window is one pane).  A key
+    // whose element count is a multiple of size was just purged and holds no state.  The
+    // sliding form keeps the version-3 layout.
+    int snapshot_count_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
+        int rc;
+        KhmHost kh;
         std::vector<int64_t> ent;
         std::vector<int32_t> kgs;
-        if ((rc = session_collect(sess, kg_lo, kg_hi, ent, kgs, err,
-                                  hashed ? std::function<int32_t(int64_t)>([&](int64_t k) { return kh.hash(k); })
-                                         : std::function<int32_t(int64_t)>())))
-            return fail(rc, "%s", err.c_str());
+        if ((rc = collect_slots(kg_lo, kg_hi, kh, ent, kgs))) return rc;
         const int64_t ew = session_entry_words(sess), W = tv.words;
         const int64_t ring = (ew - 2) / W;
         const int nk = kg_hi - kg_lo + 1;
@@ -2298,136 +2260,88 @@ struct gw_handle {
             const int64_t c = ent[ew * i + 1];
             if (c % cfg.size != 0) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
         }
-        std::vector<uint8_t> pay;
-        std::vector<int64_t> offs(nk + 1, 0);
+        snap::Writer w;
         for (int g = 0; g < nk; ++g) {
-            offs[g] = (int64_t)pay.size();
+            w.begin_group();
             auto& ix = by_kg[g];
             std::sort(ix.begin(), ix.end(), [&](int64_t x, int64_t y) { return ent[ew * x] < ent[ew * y]; });
-            std::vector<uint8_t> cnt;
-            be32(pay, (int32_t)ix.size());
-            be32(cnt, (int32_t)ix.size());
+            std::vector<uint8_t> st, cnt;
             for (int64_t i : ix) {
                 const int64_t* e = &ent[ew * i];
                 const int64_t key = e[0], c = e[1];
                 const int64_t* cell = e + 2 + (((c - 1) / cfg.size) % ring) * W;  // the current count pane
-                pay.push_back(0);
-                be64(pay, key);
-                if (hashed) be32(pay, kh.hash(key));
-                acc_to_be(pay, cell[0], W == 2 ? cell[1] : 0);
-                cnt.push_back(0);
-                be64(cnt, key);
-                if (hashed) be32(cnt, kh.hash(key));
-                be64(cnt, c % cfg.size);
+                for (std::vector<uint8_t>* v : {&st, &cnt}) {  // (GlobalWindow, key, [hash,] ...
+                    v->push_back(0);
+                    snap::put64(*v, key);
+                    if (kh.on()) snap::put32(*v, kh.hash(key));
+                }
+                acc_to_be(st, cell[0], W == 2 ? cell[1] : 0);
+                snap::put64(cnt, c % cfg.size);
             }
-            pay.insert(pay.end(), cnt.begin(), cnt.end());
-            be32(pay, 0);
+            w.section((int32_t)ix.size(), st);
+            w.section((int32_t)ix.size(), cnt);
+            w.section(0, {});  // no timers
         }
-        offs[nk] = (int64_t)pay.size();
-        const int64_t need = (int64_t)sizeof(SnapHeader) + (int64_t)(nk + 1) * 8 + (int64_t)pay.size();
-        *len = need;
-        if (!buf) return GW_OK;
-        if (cap < need) return fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)need);
-        SnapHeader hd{};
-        memcpy(hd.magic, "GWS1", 4);
-        hd.version = 4;
-        hd.agg = cfg.agg; hd.assigner = cfg.assigner;
-        hd.size = cfg.size; hd.slide = cfg.slide; hd.offset = cfg.offset; hd.gap = cfg.gap;
-        hd.flags = hashed ? kSnapKeyHashes : 0;
-        hd.max_parallelism = cfg.max_parallelism; hd.kg_lo = kg_lo; hd.kg_hi = kg_hi;
-        hd.entries = (int64_t)pay.size();
-        char* out = (char*)buf;
-        memcpy(out, &hd, sizeof hd);
-        memcpy(out + sizeof hd, offs.data(), (nk + 1) * 8);
-        if (!pay.empty()) memcpy(out + sizeof hd + (nk + 1) * 8, pay.data(), pay.size());
-        return GW_OK;
+        return finish_blob(w, blob_header(4, kg_lo, kg_hi, kh.on()), buf, cap, len);
     }
     // ... and back into version-3 entries (key, element count = the trigger's count, the
     // contents in count pane 0 of the ring, identities elsewhere)
-    int parse_count_heap(const SnapHeader& hd, const uint8_t* p, const uint8_t* end, std::vector<int64_t>& ent,
-                         std::vector<int64_t>& hkeys, std::vector<int32_t>& hvals) {
-        const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-        const int hb = (hd.flags & kSnapKeyHashes) ? 4 : 0, ab = acc_bytes();
+    int parse_count_heap(const snap::Header& hd, snap::Cursor c, std::vector<int64_t>& ent, std::vector<int64_t>& hkeys,
+                         std::vector<int32_t>& hvals) {
+        const int64_t at = snap::count_value_at(hd);
+        const bool hashed = snap::hash_bytes(hd) != 0;
         const int64_t ew = session_entry_words(sess), W = tv.words;
-#define NEED(x) do { if ((int64_t)(x) > end - p) return fail(GW_E_INVALID, "truncated snapshot blob"); } while (0)
-        for (int64_t g = 0; g < nk; ++g) {
-            NEED(4);
-            const int32_t n = rd32(p);
-            p += 4;
-            if (n < 0) return fail(GW_E_INVALID, "corrupt snapshot blob");
-            NEED((int64_t)n * (9 + hb + ab));
-            const uint8_t* st = p;
-            p += (int64_t)n * (9 + hb + ab);
-            NEED(4);
-            const int32_t m = rd32(p);
-            p += 4;
-            if (m != n) return fail(GW_E_INVALID, "count-window contents without their CountTrigger count");
-            NEED((int64_t)m * (17 + hb));
-            for (int32_t i = 0; i < n; ++i) {
-                const uint8_t* x = st + (int64_t)i * (9 + hb + ab);
-                const uint8_t* c = p + (int64_t)i * (17 + hb);
-                const int64_t key = rd64(x + 1), cnt = rd64(c + 9 + hb);
-                if (x[0] != 0 || c[0] != 0 || rd64(c + 1) != key || cnt <= 0 || cnt >= cfg.size)
-                    return fail(GW_E_INVALID, "corrupt count-window snapshot entry");
-                if (hb) { hkeys.push_back(key); hvals.push_back(rd32(x + 9)); }
-                const size_t at = ent.size();
-                ent.resize(at + (size_t)ew, 0);
-                ent[at] = key;
-                ent[at + 1] = cnt;
-                for (int64_t q = 2; q < ew; q += W) {  // identities, then the contents in pane 0
-                    ent[at + q] = identity0(cfg.agg);
-                    if (W == 2) ent[at + q + 1] = 0;
+        snap::Entries st{};
+        const snap::Err e = snap::walk_count_windows(
+            hd, c, [&](snap::Entries contents) { st = contents; },
+            [&](snap::Entries counts) {
+                if (counts.n != st.n) return snap::invalid("count-window contents without their CountTrigger count");
+                for (int32_t i = 0; i < st.n; ++i) {
+                    const uint8_t* x = st[i];
+                    const uint8_t* q = counts[i];
+                    const int64_t key = snap::get64(x + snap::kCountKeyAt), cnt = snap::get64(q + at);
+                    if (x[0] != 0 || q[0] != 0 || snap::get64(q + snap::kCountKeyAt) != key || cnt <= 0 || cnt >= cfg.size)
+                        return snap::invalid("corrupt count-window snapshot entry");
+                    if (hashed) {
+                        hkeys.push_back(key);
+                        hvals.push_back(snap::get32(x + snap::kCountHashAt));
+                    }
+                    const size_t o = ent.size();
+                    ent.resize(o + (size_t)ew, 0);
+                    ent[o] = key;
+                    ent[o + 1] = cnt;
+                    // identities, then the contents in pane 0
+                    for (int64_t r = 2; r < ew; r += W) ent[o + r] = identity0(cfg.agg);
+                    int64_t a0, a1;
+                    acc_from_be(x + at, a0, a1);
+                    ent[o + 2] = a0;
+                    if (W == 2) ent[o + 3] = a1;
                 }
-                int64_t a0, a1;
-                acc_from_be(x + 9 + hb, a0, a1);
-                ent[at + 2] = a0;
-                if (W == 2) ent[at + 3] = a1;
-            }
-            p += (int64_t)m * (17 + hb);
-            NEED(4);
-            if (rd32(p) != 0) return fail(GW_E_INVALID, "count windows hold no timers");
-            p += 4;
-        }
-#undef NEED
-        if (p != end) return fail(GW_E_INVALID, "snapshot blob has trailing bytes");
-        return GW_OK;
+                return snap::Err{};
+            });
+        return e ? fail(e) : GW_OK;
     }
 
-    // Session windows in the heap backend's layout (HeapSnapshotStrategy.java:97-154), per key
-    // group and big-endian like snapshot_heap:
-    //   "window-contents": be32 n; n x (state window, key, [be32 key hash,] accumulator): one
-    //       entry per in-flight session holding state (CopyOnWriteStateMapSnapshot.writeState
-    //       :127-149).  The GPU keeps a session's state under the session itself, so its state
-    //       window is the window; a fired session under PurgingTrigger holds no state (its
-    //       contents were purged, WindowOperator.java:482-484) and has no entry;
-    //   "merging-window-set": be32 m; m x (key, [be32 key hash,] be32 c, c x (window, state
-    //       window)): the key's MergingWindowSet mapping (MergingWindowSet.persist :99-106);
-    //   timers: be32 t; t x (flipSignBit(ts), key, window) (TimerSerializer :147-152): the
-    //       trigger's timer at maxTimestamp while the session has not fired
-    //       (EventTimeTrigger.onElement / onMerge) and, under allowed lateness, its cleanup
-    //       timer (registerCleanupTimer :631-643; with lateness 0 the two coincide).
+    // Session windows in the heap backend's layout (snap::walk_windows).  The GPU keeps a
+    // session's state under the session itself, so its state window is the window; a fired
+    // session under PurgingTrigger holds no state (its contents were purged,
+    // WindowOperator.java:482-484) and has no entry.  Timers: the trigger's timer at
+    // maxTimestamp while the session has not fired (EventTimeTrigger.onElement / onMerge)
+    // and, under allowed lateness, its cleanup timer.
     // Order: keys ascending, a key's sessions by start, its timers by (window, time).
     int snapshot_sessions_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
         int rc;
-        if ((rc = session_refresh(sess, err))) return fail(rc, "%s", err.c_str());
         KhmHost kh;
-        if ((rc = khm_host(kh))) return rc;
-        const bool hashed = kh.on();
         std::vector<int64_t> ent;  // (key, start, end, a0, a1, fired) per session
         std::vector<int32_t> kgs;
-        if ((rc = session_collect(sess, kg_lo, kg_hi, ent, kgs, err,
-                                  hashed ? std::function<int32_t(int64_t)>([&](int64_t k) { return kh.hash(k); })
-                                         : std::function<int32_t(int64_t)>())))
-            return fail(rc, "%s", err.c_str());
+        if ((rc = collect_slots(kg_lo, kg_hi, kh, ent, kgs))) return rc;
         const int nk = kg_hi - kg_lo + 1;
         std::vector<std::vector<int64_t>> by_kg(nk);
         for (size_t i = 0; i < kgs.size(); ++i) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
         const bool purging = cfg.trigger == GW_PURGING_EVENT_TIME_TRIGGER;
-        const i128 LMAX = INT64_MAX;
-        std::vector<uint8_t> pay;
-        std::vector<int64_t> offs(nk + 1, 0);
+        snap::Writer w;
         for (int g = 0; g < nk; ++g) {
-            offs[g] = (int64_t)pay.size();
+            w.begin_group();
             auto& ix = by_kg[g];
             std::sort(ix.begin(), ix.end(), [&](int64_t x, int64_t y) {
                 const int64_t* a = &ent[6 * x];
@@ -2440,61 +2354,28 @@ struct gw_handle {
                 const int64_t key = ent[6 * ix[a]];
                 size_t b = a;
                 while (b < ix.size() && ent[6 * ix[b]] == key) ++b;
-                be64(ms, key);
-                if (hashed) be32(ms, kh.hash(key));
-                be32(ms, (int32_t)(b - a));
+                snap::put64(ms, key);
+                if (kh.on()) snap::put32(ms, kh.hash(key));
+                snap::put32(ms, (int32_t)(b - a));
                 nms++;
                 for (size_t q = a; q < b; ++q) {
                     const int64_t* x = &ent[6 * ix[q]];
                     const int64_t s0 = x[1], e0 = x[2];
                     const bool fired = x[5] != 0;
-                    be64(ms, s0); be64(ms, e0); be64(ms, s0); be64(ms, e0);
+                    snap::put64(ms, s0); snap::put64(ms, e0); snap::put64(ms, s0); snap::put64(ms, e0);
                     if (!(purging && fired)) {
-                        be64(st, s0); be64(st, e0); be64(st, key);
-                        if (hashed) be32(st, kh.hash(key));
-                        acc_to_be(st, x[3], x[4]);
+                        put_state(st, s0, e0, key, kh, x[3], x[4]);
                         nst++;
                     }
-                    const i128 mx = (i128)e0 - 1;
-                    if (!fired) {
-                        be64(tm, (int64_t)((uint64_t)(int64_t)mx ^ 0x8000000000000000ull));
-                        be64(tm, key); be64(tm, s0); be64(tm, e0);
-                        ntm++;
-                    }
-                    const i128 ct = mx + (i128)cfg.allowed_lateness;
-                    if (cfg.allowed_lateness > 0 && ct < LMAX) {
-                        be64(tm, (int64_t)((uint64_t)(int64_t)ct ^ 0x8000000000000000ull));
-                        be64(tm, key); be64(tm, s0); be64(tm, e0);
-                        ntm++;
-                    }
+                    put_window_timers(tm, ntm, !fired, key, s0, e0);
                 }
                 a = b;
             }
-            be32(pay, nst);
-            pay.insert(pay.end(), st.begin(), st.end());
-            be32(pay, nms);
-            pay.insert(pay.end(), ms.begin(), ms.end());
-            be32(pay, ntm);
-            pay.insert(pay.end(), tm.begin(), tm.end());
+            w.section(nst, st);
+            w.section(nms, ms);
+            w.section(ntm, tm);
         }
-        offs[nk] = (int64_t)pay.size();
-        const int64_t need = (int64_t)sizeof(SnapHeader) + (int64_t)(nk + 1) * 8 + (int64_t)pay.size();
-        *len = need;
-        if (!buf) return GW_OK;
-        if (cap < need) return fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)need);
-        SnapHeader hd{};
-        memcpy(hd.magic, "GWS1", 4);
-        hd.version = 4;
-        hd.agg = cfg.agg; hd.assigner = cfg.assigner;
-        hd.size = cfg.size; hd.slide = cfg.slide; hd.offset = cfg.offset; hd.gap = cfg.gap;
-        hd.flags = hashed ? kSnapKeyHashes : 0;
-        hd.max_parallelism = cfg.max_parallelism; hd.kg_lo = kg_lo; hd.kg_hi = kg_hi;
-        hd.entries = (int64_t)pay.size();
-        char* out = (char*)buf;
-        memcpy(out, &hd, sizeof hd);
-        memcpy(out + sizeof hd, offs.data(), (nk + 1) * 8);
-        if (!pay.empty()) memcpy(out + sizeof hd + (nk + 1) * 8, pay.data(), pay.size());
-        return GW_OK;
+        return finish_blob(w, blob_header(4, kg_lo, kg_hi, kh.on()), buf, cap, len);
     }
 
     // Reads a session blob of the heap layout back into (key, start, end, a0, a1, fired)
@@ -2504,79 +2385,68 @@ struct gw_handle {
     // maxTimestamp is gone.  A session without state that has not fired is a trigger outside
     // EventTimeTrigger / PurgingTrigger (GW_E_UNSUPPORTED); state no mapping names, or
     // overlapping sessions of one key, are a corrupt blob.
-    int parse_session_heap(const SnapHeader& hd, const uint8_t* p, const uint8_t* end, std::vector<int64_t>& out,
-                           std::vector<int64_t>& hkeys, std::vector<int32_t>& hvals) {
-        const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-        const int ab = acc_bytes();
-        const int hb = (hd.flags & kSnapKeyHashes) ? 4 : 0;
+    int parse_session_heap(const snap::Header& hd, snap::Cursor c, std::vector<int64_t>& out, std::vector<int64_t>& hkeys,
+                           std::vector<int32_t>& hvals) {
+        const bool hashed = snap::hash_bytes(hd) != 0;
+        const int64_t acc_at = snap::state_acc_at(hd);
         const int64_t id0 = cfg.agg == GW_AVG_F64 ? INT64_MIN : identity0(cfg.agg);  // a purged session
         typedef std::tuple<int64_t, int64_t, int64_t> KW;  // (key, start, end)
-#define NEED(x) do { if ((x) < 0 || (int64_t)(x) > end - p) return fail(GW_E_INVALID, "truncated snapshot blob"); } while (0)
-        for (int64_t g = 0; g < nk; ++g) {
-            NEED(4);
-            const int32_t ns = rd32(p); p += 4;
-            if (ns < 0) return fail(GW_E_INVALID, "negative entry count in snapshot key group");
-            NEED((int64_t)ns * (24 + hb + ab));
-            std::map<KW, std::pair<std::pair<int64_t, int64_t>, bool>> state;  // -> (acc, used)
-            for (int32_t i = 0; i < ns; ++i, p += 24 + hb + ab) {
-                const int64_t s0 = rd64(p), e0 = rd64(p + 8), key = rd64(p + 16);
+        // of the current key group:
+        std::map<KW, std::pair<std::pair<int64_t, int64_t>, bool>> state;  // -> (acc, used)
+        std::vector<std::array<int64_t, 5>> ses;  // (key, start, end, state start, state end)
+        std::set<KW> armed;  // sessions whose trigger timer (at maxTimestamp) is still set
+        const snap::Err e = snap::walk_windows(
+            hd, c,
+            [&](const uint8_t* p) {
+                const int64_t key = snap::state_key(p);
                 int64_t a0, a1;
-                acc_from_be(p + 24 + hb, a0, a1);
-                if (hb) { hkeys.push_back(key); hvals.push_back(rd32(p + 24)); }
-                if (!state.emplace(KW{key, s0, e0}, std::make_pair(std::make_pair(a0, a1), false)).second)
-                    return fail(GW_E_INVALID, "two state entries of one (key, window) in a snapshot key group");
-            }
-            NEED(4);
-            const int32_t nm = rd32(p); p += 4;
-            if (nm < 0) return fail(GW_E_INVALID, "negative merging window set count in snapshot key group");
-            std::vector<std::array<int64_t, 5>> ses;  // (key, start, end, state start, state end)
-            for (int32_t i = 0; i < nm; ++i) {
-                NEED(12 + hb);
-                const int64_t key = rd64(p);
-                if (hb) { hkeys.push_back(key); hvals.push_back(rd32(p + 8)); }
-                const int32_t c = rd32(p + 8 + hb);
-                p += 12 + hb;
-                if (c < 0) return fail(GW_E_INVALID, "negative merging window set size");
-                NEED((int64_t)c * 32);
-                for (int32_t j = 0; j < c; ++j, p += 32)
-                    ses.push_back({key, rd64(p), rd64(p + 8), rd64(p + 16), rd64(p + 24)});
-            }
-            NEED(4);
-            const int32_t nt = rd32(p); p += 4;
-            if (nt < 0) return fail(GW_E_INVALID, "negative timer count in snapshot key group");
-            NEED((int64_t)nt * 32);
-            std::set<KW> armed;  // sessions whose trigger timer (at maxTimestamp) is still set
-            for (int32_t i = 0; i < nt; ++i, p += 32) {
-                const int64_t ts = (int64_t)((uint64_t)rd64(p) ^ 0x8000000000000000ull);
-                const int64_t key = rd64(p + 8), s0 = rd64(p + 16), e0 = rd64(p + 24);
-                if (ts == (int64_t)((uint64_t)e0 - 1)) armed.insert(KW{key, s0, e0});
-            }
-            std::sort(ses.begin(), ses.end());
-            for (size_t i = 0; i < ses.size(); ++i) {
-                const auto& x = ses[i];
-                if (x[2] <= x[1]) return fail(GW_E_INVALID, "empty session window in a snapshot");
-                if (i && ses[i - 1][0] == x[0] && ses[i - 1][2] >= x[1])  // TimeWindow.intersects is inclusive
-                    return fail(GW_E_INVALID, "overlapping sessions of one key in a snapshot");
-                const bool fired = armed.count(KW{x[0], x[1], x[2]}) == 0;
-                auto it = state.find(KW{x[0], x[3], x[4]});
-                int64_t a0 = id0, a1 = 0;
-                if (it != state.end()) {
-                    if (it->second.second) return fail(GW_E_INVALID, "two sessions share one state window");
-                    it->second.second = true;
-                    a0 = it->second.first.first;
-                    a1 = it->second.first.second;
-                } else if (!fired) {
-                    return fail(GW_E_UNSUPPORTED, "a session without state whose timer has not fired "
-                                                  "(a trigger other than EventTimeTrigger / PurgingTrigger)");
+                acc_from_be(p + acc_at, a0, a1);
+                if (hashed) { hkeys.push_back(key); hvals.push_back(snap::state_hash(p)); }
+                const KW kw{key, snap::state_start(p), snap::state_end(p)};
+                if (!state.emplace(kw, std::make_pair(std::make_pair(a0, a1), false)).second)
+                    return snap::invalid("two state entries of one (key, window) in a snapshot key group");
+                return snap::Err{};
+            },
+            [&](const uint8_t* head, int32_t n, const uint8_t* win) {
+                const int64_t key = snap::get64(head);
+                if (hashed) { hkeys.push_back(key); hvals.push_back(snap::get32(head + snap::kSetHashAt)); }
+                for (int32_t j = 0; j < n; ++j, win += snap::kSetWindowBytes)
+                    ses.push_back({key, snap::get64(win), snap::get64(win + 8), snap::get64(win + 16), snap::get64(win + 24)});
+            },
+            [&](const uint8_t* t) {
+                const int64_t e0 = snap::timer_end(t);
+                if (snap::timer_time(t) == (int64_t)((uint64_t)e0 - 1))
+                    armed.insert(KW{snap::timer_key(t), snap::timer_start(t), e0});
+            },
+            [&] {
+                std::sort(ses.begin(), ses.end());
+                for (size_t i = 0; i < ses.size(); ++i) {
+                    const auto& x = ses[i];
+                    if (x[2] <= x[1]) return snap::invalid("empty session window in a snapshot");
+                    if (i && ses[i - 1][0] == x[0] && ses[i - 1][2] >= x[1])  // TimeWindow.intersects is inclusive
+                        return snap::invalid("overlapping sessions of one key in a snapshot");
+                    const bool fired = armed.count(KW{x[0], x[1], x[2]}) == 0;
+                    auto it = state.find(KW{x[0], x[3], x[4]});
+                    int64_t a0 = id0, a1 = 0;
+                    if (it != state.end()) {
+                        if (it->second.second) return snap::invalid("two sessions share one state window");
+                        it->second.second = true;
+                        a0 = it->second.first.first;
+                        a1 = it->second.first.second;
+                    } else if (!fired) {
+                        return snap::Err{GW_E_UNSUPPORTED, "a session without state whose timer has not fired "
+                                                           "(a trigger other than EventTimeTrigger / PurgingTrigger)"};
+                    }
+                    out.insert(out.end(), {x[0], x[1], x[2], a0, a1, (int64_t)fired});
                 }
-                out.insert(out.end(), {x[0], x[1], x[2], a0, a1, (int64_t)fired});
-            }
-            for (auto& kv : state)
-                if (!kv.second.second) return fail(GW_E_INVALID, "a state entry outside every merging window set");
-        }
-#undef NEED
-        if (p != end) return fail(GW_E_INVALID, "snapshot blob has trailing bytes");
-        return GW_OK;
+                for (auto& kv : state)
+                    if (!kv.second.second) return snap::invalid("a state entry outside every merging window set");
+                state.clear();
+                ses.clear();
+                armed.clear();
+                return snap::Err{};
+            });
+        return e ? fail(e) : GW_OK;
     }
 
     int snapshot_sessions(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
@@ -2585,123 +2455,69 @@ struct gw_handle {
             return fail(GW_E_INVALID, "key-group range [%d, %d] outside [0, %d)", kg_lo, kg_hi, cfg.max_parallelism);
         if (cfg.assigner == GW_SESSION) return snapshot_sessions_heap(kg_lo, kg_hi, buf, cap, len);
         if (cfg.assigner == GW_COUNT_TUMBLING) return snapshot_count_heap(kg_lo, kg_hi, buf, cap, len);
-        if ((rc = session_refresh(sess, err))) return fail(rc, "%s", err.c_str());
         KhmHost kh;
-        if ((rc = khm_host(kh))) return rc;
-        const bool hashed = kh.on();
         std::vector<int64_t> ent;
         std::vector<int32_t> kgs;
-        if ((rc = session_collect(sess, kg_lo, kg_hi, ent, kgs, err,
-                                  hashed ? std::function<int32_t(int64_t)>([&](int64_t k) { return kh.hash(k); })
-                                         : std::function<int32_t(int64_t)>())))
-            return fail(rc, "%s", err.c_str());
-        const int64_t ew0 = session_entry_words(sess);
-        if (hashed) {  // each entry gets the key's hash as one more word
-            std::vector<int64_t> w;
-            w.reserve(ent.size() / ew0 * (ew0 + 1));
-            for (size_t i = 0; i < ent.size(); i += ew0) {
-                w.insert(w.end(), ent.begin() + i, ent.begin() + i + ew0);
-                w.push_back((int64_t)kh.hash(ent[i]));
-            }
-            ent.swap(w);
-        }
-        const int64_t ew = ew0 + (hashed ? 1 : 0);
+        if ((rc = collect_slots(kg_lo, kg_hi, kh, ent, kgs))) return rc;
+        // fixed entries in key-group order, collection order within a key group; with key
+        // hashes each entry gets the key's hash as one more word
+        const int64_t ew = session_entry_words(sess);
         const int nk = kg_hi - kg_lo + 1;
-        std::vector<int64_t> offs(nk + 1, 0);
-        for (int32_t k : kgs) offs[k - kg_lo + 1]++;
-        for (int i = 0; i < nk; ++i) offs[i + 1] += offs[i];
-        const int64_t need = (int64_t)sizeof(SnapHeader) + (int64_t)(nk + 1) * 8 + (int64_t)kgs.size() * ew * 8;
-        *len = need;
-        if (!buf) return GW_OK;
-        if (cap < need) return fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)need);
-        SnapHeader hd{};
-        memcpy(hd.magic, "GWS1", 4);
-        hd.version = slot_blob_version();
-        hd.agg = cfg.agg; hd.assigner = cfg.assigner;
-        hd.size = cfg.size; hd.slide = cfg.slide; hd.gap = cfg.gap;
-        hd.max_parallelism = cfg.max_parallelism; hd.kg_lo = kg_lo; hd.kg_hi = kg_hi;
-        hd.reserved = (int32_t)ew;
-        hd.flags = hashed ? kSnapKeyHashes : 0;
-        hd.entries = (int64_t)kgs.size();
-        char* out = (char*)buf;
-        memcpy(out, &hd, sizeof hd);
-        memcpy(out + sizeof hd, offs.data(), (nk + 1) * 8);
-        int64_t* oe = (int64_t*)(out + sizeof hd + (nk + 1) * 8);
-        std::vector<int64_t> fill(offs.begin(), offs.end() - 1);
-        for (size_t i = 0; i < kgs.size(); ++i) memcpy(oe + ew * fill[kgs[i] - kg_lo]++, &ent[ew * i], ew * 8);
-        return GW_OK;
+        std::vector<std::vector<int64_t>> by_kg(nk);
+        for (size_t i = 0; i < kgs.size(); ++i) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
+        snap::Writer w;
+        for (int g = 0; g < nk; ++g) {
+            w.begin_group();
+            for (int64_t i : by_kg[g]) {
+                w.bytes((const uint8_t*)&ent[ew * i], ew * 8);
+                if (kh.on()) {
+                    const int64_t hw = (int64_t)kh.hash(ent[ew * i]);
+                    w.bytes((const uint8_t*)&hw, 8);
+                }
+            }
+        }
+        snap::Header hd = blob_header(slot_blob_version(), kg_lo, kg_hi, kh.on());
+        hd.offset = 0;
+        hd.reserved = (int32_t)(ew + (kh.on() ? 1 : 0));
+        return finish_blob(w, hd, buf, cap, len);
     }
 
     int restore_sessions(const void* buf, int64_t len, bool dry = false) {
-        if (!buf || len < (int64_t)sizeof(SnapHeader)) return fail(GW_E_INVALID, "snapshot blob too short");
-        SnapHeader hd;
-        memcpy(&hd, buf, sizeof hd);
-        if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version < 1 || hd.version > kSnapMaxVersion)
-            return fail(GW_E_INVALID, "not a gpuwin snapshot");
-        if (cfg.assigner == GW_SESSION) {
-            if (hd.version != 4 || hd.agg != cfg.agg || hd.assigner != cfg.assigner || hd.gap != cfg.gap ||
-                hd.max_parallelism != cfg.max_parallelism || (hd.flags & ~kSnapKeyHashes))
-                return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-            const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-            const int64_t pay0 = (int64_t)sizeof hd + (nk + 1) * 8;
-            if (nk <= 0 || hd.entries < 0 || len < pay0 || hd.entries > len - pay0)
-                return fail(GW_E_INVALID, "truncated snapshot blob");
-            const uint8_t* p = (const uint8_t*)buf + pay0;
-            std::vector<int64_t> ent, hkeys;
-            std::vector<int32_t> hvals;
-            int rc = parse_session_heap(hd, p, p + hd.entries, ent, hkeys, hvals);
-            if (rc == GW_OK) rc = khm_check_host(hkeys, hvals);  // before the table changes
-            if (rc || dry) return rc;
-            rc = session_restore(sess, ent.data(), (int64_t)(ent.size() / 6), err);
-            if (rc) return fail(rc, "%s", err.c_str());
-            return khm_insert_host(hkeys, hvals);
-        }
-        if (cfg.assigner == GW_COUNT_TUMBLING) {
-            if (hd.version != 4 || hd.agg != cfg.agg || hd.assigner != cfg.assigner || hd.size != cfg.size ||
-                hd.max_parallelism != cfg.max_parallelism || (hd.flags & ~kSnapKeyHashes))
-                return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-            const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-            const int64_t pay0 = (int64_t)sizeof hd + (nk + 1) * 8;
-            if (nk <= 0 || hd.entries < 0 || len < pay0 || hd.entries > len - pay0)
-                return fail(GW_E_INVALID, "truncated snapshot blob");
-            const uint8_t* p = (const uint8_t*)buf + pay0;
-            std::vector<int64_t> ent, hkeys;
-            std::vector<int32_t> hvals;
-            int rc = parse_count_heap(hd, p, p + hd.entries, ent, hkeys, hvals);
-            if (rc == GW_OK) rc = khm_check_host(hkeys, hvals);
-            if (rc || dry) return rc;
-            rc = session_restore(sess, ent.data(), (int64_t)(ent.size() / session_entry_words(sess)), err);
-            if (rc) return fail(rc, "%s", err.c_str());
-            return khm_insert_host(hkeys, hvals);
-        }
-        const bool hashed = (hd.flags & kSnapKeyHashes) != 0;
-        const int64_t ew0 = session_entry_words(sess), ew = ew0 + (hashed ? 1 : 0);
-        if (hd.version != slot_blob_version() || hd.agg != cfg.agg || hd.assigner != cfg.assigner ||
-            hd.gap != cfg.gap || hd.size != cfg.size || hd.slide != cfg.slide ||
-            hd.max_parallelism != cfg.max_parallelism || hd.reserved != (int32_t)ew)
-            return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-        const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-        const int64_t hdr = (int64_t)sizeof hd + (nk + 1) * 8;
-        if (nk <= 0 || hd.entries < 0 || len < hdr || hd.entries > (len - hdr) / (ew * 8))
-            return fail(GW_E_INVALID, "truncated snapshot blob");
-        const int64_t* in = (const int64_t*)((const char*)buf + hdr);
+        snap::Header hd;
+        snap::Cursor c;
+        snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
+        if (e) return fail(e);
+        const int64_t ew0 = session_entry_words(sess), ew = ew0 + snap::hash_bytes(hd) / 4;  // fixed entries: words
+        bool same = hd.version == slot_blob_version() && hd.agg == cfg.agg && hd.assigner == cfg.assigner &&
+                    hd.max_parallelism == cfg.max_parallelism;
+        if (cfg.assigner == GW_SESSION) same = same && hd.gap == cfg.gap && !(hd.flags & ~snap::kKeyHashes);
+        else if (cfg.assigner == GW_COUNT_TUMBLING) same = same && hd.size == cfg.size && !(hd.flags & ~snap::kKeyHashes);
+        else same = same && hd.gap == cfg.gap && hd.size == cfg.size && hd.slide == cfg.slide && hd.reserved == (int32_t)ew;
+        if (!same) return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
+        if ((e = snap::payload(buf, len, hd, c))) return fail(e);
         std::vector<int64_t> ent, hkeys;
         std::vector<int32_t> hvals;
-        ent.reserve((size_t)(hd.entries * ew0));
-        for (int64_t i = 0; i < hd.entries; ++i) {  // aligned copy without the hash words
-            const size_t at = ent.size();
-            ent.resize(at + (size_t)ew0);
-            memcpy(ent.data() + at, (const char*)in + i * ew * 8, (size_t)ew0 * 8);
-            if (hashed) {
-                int64_t hw;
-                memcpy(&hw, (const char*)in + (i * ew + ew0) * 8, 8);
-                hkeys.push_back(ent[at]);
-                hvals.push_back((int32_t)hw);
+        int rc = GW_OK;
+        if (cfg.assigner == GW_SESSION) {
+            rc = parse_session_heap(hd, c, ent, hkeys, hvals);
+        } else if (cfg.assigner == GW_COUNT_TUMBLING) {
+            rc = parse_count_heap(hd, c, ent, hkeys, hvals);
+        } else {
+            ent.resize((size_t)(hd.entries * ew0));
+            for (int64_t i = 0; i < hd.entries; ++i) {  // aligned copy without the hash words
+                const uint8_t* x = c.take(ew * 8);
+                memcpy(&ent[i * ew0], x, (size_t)ew0 * 8);
+                if (ew > ew0) {
+                    int64_t hw;
+                    memcpy(&hw, x + ew0 * 8, 8);
+                    hkeys.push_back(ent[i * ew0]);
+                    hvals.push_back((int32_t)hw);
+                }
             }
         }
-        int rc = khm_check_host(hkeys, hvals);  // before the table changes
+        if (rc == GW_OK) rc = khm_check_host(hkeys, hvals);  // before the table changes
         if (rc || dry) return rc;
-        rc = session_restore(sess, ent.data(), hd.entries, err);
+        rc = session_restore(sess, ent.data(), (int64_t)ent.size() / ew0, err);
         if (rc) return fail(rc, "%s", err.c_str());
         return khm_insert_host(hkeys, hvals);
     }
@@ -4128,155 +3944,127 @@ int gw_flush(gw_handle* h) {
 // Window-class composite snapshots: the children's heap-layout blobs merged per key group
 // (their (window, key, state) entries and timers are disjoint by window), under the
 // composite's own assigner header; restore splits each key group's entries and timers by
-// the class of their window.  Layout per key group (snapshot_heap): be32 n + n entries of
-// (start, end, key, state), be32 0 (no merging window set), be32 t + t timers of 32 bytes.
-typedef gw_handle::SnapHeader SnapHdr;
+// the class of their window.  The layout: snap::walk_windows, without merging window sets.
 static int64_t comp_slide(const gw_handle* h) { return h->cfg.assigner == GW_TUMBLING ? h->cfg.size : h->cfg.slide; }
+static int kid_snapshot(gw_handle* h, gw_handle* kid, int32_t kg_lo, int32_t kg_hi, std::vector<uint8_t>& blob) {
+    int64_t l = 0;
+    int rc = gw_snapshot(kid, kg_lo, kg_hi, nullptr, 0, &l);
+    if (rc) return kid_rc(h, kid, rc);
+    blob.resize((size_t)l);
+    if ((rc = gw_snapshot(kid, kg_lo, kg_hi, blob.data(), l, &l))) return kid_rc(h, kid, rc);
+    return GW_OK;
+}
+
 static int comp_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
     const int64_t nk = (int64_t)kg_hi - kg_lo + 1;
     if (kg_lo < 0 || nk <= 0) return h->fail(GW_E_INVALID, "bad key-group range");
     std::vector<std::vector<uint8_t>> blobs(h->kids.size());
-    int64_t flags = -1;
+    // per key group, the classes' entries by (key, window) and timers by (key, window, time bytes)
+    std::vector<std::vector<std::pair<std::pair<int64_t, int64_t>, const uint8_t*>>> st(nk);
+    std::vector<std::vector<std::pair<std::tuple<int64_t, int64_t, uint64_t>, const uint8_t*>>> tm(nk);
+    snap::Header hd{};  // kids[0]'s: every class sees every batch, so all or none carry key hashes
     for (size_t j = 0; j < h->kids.size(); ++j) {
-        int64_t l = 0;
-        int rc = gw_snapshot(h->kids[j], kg_lo, kg_hi, nullptr, 0, &l);
-        if (rc) return kid_rc(h, h->kids[j], rc);
-        blobs[j].resize((size_t)l);
-        if ((rc = gw_snapshot(h->kids[j], kg_lo, kg_hi, blobs[j].data(), l, &l))) return kid_rc(h, h->kids[j], rc);
-        SnapHdr kh;
-        memcpy(&kh, blobs[j].data(), sizeof kh);
-        if (flags >= 0 && kh.flags != flags) return h->fail(GW_E_STATE, "window classes disagree on key hashes");
-        flags = kh.flags;
+        int rc = kid_snapshot(h, h->kids[j], kg_lo, kg_hi, blobs[j]);
+        if (rc) return rc;
+        snap::Header kh;
+        snap::Cursor c;
+        snap::Err e = snap::open(blobs[j].data(), (int64_t)blobs[j].size(), 4, 4, kh, c);
+        if (e) return h->fail(e);
+        if (j && kh.flags != hd.flags) return h->fail(GW_E_STATE, "window classes disagree on key hashes");
+        if (!j) hd = kh;
+        int64_t g = 0;
+        e = snap::walk_windows(
+            kh, c, [&](const uint8_t* p) { st[g].push_back({{snap::state_key(p), snap::state_start(p)}, p}); }, snap::NoSets{},
+            [&](const uint8_t* t) {
+                tm[g].push_back({{snap::timer_key(t), snap::timer_start(t), (uint64_t)snap::get64(t)}, t});
+            },
+            [&] { ++g; });
+        if (e) return h->fail(e);
     }
-    // every class sees every batch, so all or none carry key hashes
-    const int64_t eb = 24 + ((flags & kSnapKeyHashes) ? 4 : 0) + h->kids[0]->acc_bytes();
-    std::vector<uint8_t> pay;
-    std::vector<int64_t> offs(nk + 1, 0);
-    const int64_t hb = (int64_t)sizeof(SnapHdr) + (nk + 1) * 8;
-    for (int64_t g = 0; g < nk; ++g) {
-        offs[g] = (int64_t)pay.size();
-        // entries in snapshot_heap's order: by key, then window; timers by key, window, time
-        std::vector<std::pair<std::pair<int64_t, int64_t>, const uint8_t*>> st;
-        std::vector<std::pair<std::tuple<int64_t, int64_t, uint64_t>, const uint8_t*>> tm;
-        for (auto& b : blobs) {
-            int64_t o0;
-            memcpy(&o0, b.data() + sizeof(SnapHdr) + g * 8, 8);
-            const uint8_t* p = b.data() + hb + o0;
-            const int32_t n = gw_handle::rd32(p);
-            p += 4;
-            for (int32_t i = 0; i < n; ++i, p += eb) st.push_back({{gw_handle::rd64(p + 16), gw_handle::rd64(p)}, p});
-            p += 4;  // the empty merging window set
-            const int32_t t = gw_handle::rd32(p);
-            p += 4;
-            for (int32_t i = 0; i < t; ++i, p += 32)
-                tm.push_back({{gw_handle::rd64(p + 8), gw_handle::rd64(p + 16), (uint64_t)gw_handle::rd64(p)}, p});
-        }
-        std::sort(st.begin(), st.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        std::sort(tm.begin(), tm.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        gw_handle::be32(pay, (int32_t)st.size());
-        for (auto& e : st) pay.insert(pay.end(), e.second, e.second + eb);
-        gw_handle::be32(pay, 0);
-        gw_handle::be32(pay, (int32_t)tm.size());
-        for (auto& e : tm) pay.insert(pay.end(), e.second, e.second + 32);
+    const int64_t eb = snap::state_entry_bytes(hd);
+    snap::Writer w;
+    for (int64_t g = 0; g < nk; ++g) {  // snapshot_heap's order
+        std::sort(st[g].begin(), st[g].end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+        std::sort(tm[g].begin(), tm[g].end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+        w.begin_group();
+        w.count((int32_t)st[g].size());
+        for (auto& e : st[g]) w.bytes(e.second, eb);
+        w.count(0);
+        w.count((int32_t)tm[g].size());
+        for (auto& e : tm[g]) w.bytes(e.second, snap::kTimerBytes);
     }
-    offs[nk] = (int64_t)pay.size();
-    const int64_t need = hb + (int64_t)pay.size();
-    *len = need;
-    if (!buf) return GW_OK;
-    if (cap < need) return h->fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)need);
-    SnapHdr hd;
-    memcpy(&hd, blobs[0].data(), sizeof hd);
     hd.assigner = h->cfg.assigner;
     hd.slide = comp_slide(h);
     hd.offset = h->cfg.offset;
-    hd.entries = (int64_t)pay.size();
-    char* out = (char*)buf;
-    memcpy(out, &hd, sizeof hd);
-    memcpy(out + sizeof hd, offs.data(), (size_t)(nk + 1) * 8);
-    if (!pay.empty()) memcpy(out + hb, pay.data(), pay.size());
-    return GW_OK;
+    return h->finish_blob(w, hd, buf, cap, len);
 }
 
 static int restore_any(gw_handle* h, const void* buf, int64_t len, bool dry);
 
-// Window classes: the blob is cut into one part per class; every part is checked (a dry
-// restore) before any class restores, so a rejected blob leaves every class as it was.
+// One blob per child.  Every part is checked first (a dry restore: header, windows, counts,
+// key hashes, restore before processing) before any child restores, so a rejected blob
+// leaves every child as it was; after that only a device error can fail.
+static int restore_parts(gw_handle* h, const std::vector<gw_handle*>& kids, const std::vector<std::vector<uint8_t>>& blobs,
+                         bool dry) {
+    for (size_t j = 0; j < kids.size(); ++j) {
+        const int rc = restore_any(kids[j], blobs[j].data(), (int64_t)blobs[j].size(), dry);
+        if (rc) return kid_rc(h, kids[j], rc);
+    }
+    return GW_OK;
+}
+
+// Window classes: the blob is cut into one part per class.
 static int comp_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
-    if (!buf || len < (int64_t)sizeof(SnapHdr)) return h->fail(GW_E_INVALID, "snapshot blob too short");
-    SnapHdr hd;
-    memcpy(&hd, buf, sizeof hd);
-    if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version != 4 || hd.agg != h->cfg.agg ||
-        hd.assigner != h->cfg.assigner || hd.size != h->cfg.size || hd.slide != comp_slide(h) ||
-        hd.offset != h->cfg.offset || hd.max_parallelism != h->cfg.max_parallelism)
+    snap::Header hd;
+    snap::Cursor c;
+    snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
+    if (e) return h->fail(e);
+    if (hd.version != 4 || hd.agg != h->cfg.agg || hd.assigner != h->cfg.assigner || hd.size != h->cfg.size ||
+        hd.slide != comp_slide(h) || hd.offset != h->cfg.offset || hd.max_parallelism != h->cfg.max_parallelism)
         return h->fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-    const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-    const int64_t hb = (int64_t)sizeof hd + (nk + 1) * 8;
-    if (nk <= 0 || hd.entries < 0 || len < hb || hd.entries > len - hb)
-        return h->fail(GW_E_INVALID, "truncated snapshot blob");
+    if ((e = snap::payload(buf, len, hd, c))) return h->fail(e);
     const int64_t J = (int64_t)h->kids.size();
-    const int64_t eb = 24 + ((hd.flags & kSnapKeyHashes) ? 4 : 0) + h->kids[0]->acc_bytes();
-    const uint8_t* p = (const uint8_t*)buf + hb;
-    const uint8_t* end = p + hd.entries;
+    snap::Header lay = hd;  // entries of the classes' width (restore_heap)
+    lay.flags &= snap::kKeyHashes;
+    const int64_t eb = snap::state_entry_bytes(lay);
     auto cls = [&](int64_t s0) {  // window class of a window start
         const int64_t k = (int64_t)floor_div((i128)s0 - h->cfg.offset, (i128)comp_slide(h));
         return (size_t)(((k % J) + J) % J);
     };
-    std::vector<std::vector<uint8_t>> pay(J);
-    std::vector<std::vector<int64_t>> offs(J, std::vector<int64_t>(nk + 1, 0));
-    for (int64_t g = 0; g < nk; ++g) {
-        std::vector<std::vector<uint8_t>> st(J), tm(J);
-        std::vector<int32_t> nst(J, 0), ntm(J, 0);
-        if (end - p < 4) return h->fail(GW_E_INVALID, "truncated snapshot blob");
-        const int32_t n = gw_handle::rd32(p);
-        p += 4;
-        if (n < 0 || (int64_t)n * eb + 8 > end - p) return h->fail(GW_E_INVALID, "truncated snapshot blob");
-        for (int32_t i = 0; i < n; ++i, p += eb) {
-            const size_t j = cls(gw_handle::rd64(p));
+    std::vector<snap::Writer> w(J);
+    std::vector<std::vector<uint8_t>> st(J), tm(J);  // of the current key group
+    e = snap::walk_windows(
+        lay, c,
+        [&](const uint8_t* p) {
+            const size_t j = cls(snap::state_start(p));
             st[j].insert(st[j].end(), p, p + eb);
-            nst[j]++;
-        }
-        if (gw_handle::rd32(p) != 0) return h->fail(GW_E_INVALID, "merging window set in a sliding snapshot");
-        p += 4;
-        const int32_t t = gw_handle::rd32(p);
-        p += 4;
-        if (t < 0 || (int64_t)t * 32 > end - p) return h->fail(GW_E_INVALID, "truncated snapshot blob");
-        for (int32_t i = 0; i < t; ++i, p += 32) {
-            const size_t j = cls(gw_handle::rd64(p + 16));  // (timestamp, key, start, end)
-            tm[j].insert(tm[j].end(), p, p + 32);
-            ntm[j]++;
-        }
-        for (int64_t j = 0; j < J; ++j) {
-            offs[j][g] = (int64_t)pay[j].size();
-            gw_handle::be32(pay[j], nst[j]);
-            pay[j].insert(pay[j].end(), st[j].begin(), st[j].end());
-            gw_handle::be32(pay[j], 0);
-            gw_handle::be32(pay[j], ntm[j]);
-            pay[j].insert(pay[j].end(), tm[j].begin(), tm[j].end());
-        }
-    }
-    if (p != end) return h->fail(GW_E_INVALID, "snapshot blob has trailing bytes");
+        },
+        snap::NoSets{"merging window set in a sliding snapshot"},
+        [&](const uint8_t* t) {
+            const size_t j = cls(snap::timer_start(t));
+            tm[j].insert(tm[j].end(), t, t + snap::kTimerBytes);
+        },
+        [&] {
+            for (int64_t j = 0; j < J; ++j) {
+                w[j].begin_group();
+                w[j].section((int32_t)(st[j].size() / eb), st[j]);
+                w[j].section(0, {});
+                w[j].section((int32_t)(tm[j].size() / snap::kTimerBytes), tm[j]);
+                st[j].clear();
+                tm[j].clear();
+            }
+        });
+    if (e) return h->fail(e);
     std::vector<std::vector<uint8_t>> blobs(J);
     for (int64_t j = 0; j < J; ++j) {
-        offs[j][nk] = (int64_t)pay[j].size();
-        SnapHdr kh = hd;
+        snap::Header kh = hd;
         kh.assigner = h->kids[j]->cfg.assigner;
         kh.slide = h->kids[j]->cfg.slide;
         kh.offset = h->kids[j]->cfg.offset;
-        kh.entries = (int64_t)pay[j].size();
-        std::vector<uint8_t>& blob = blobs[j];
-        blob.resize(sizeof kh + (nk + 1) * 8 + pay[j].size());
-        memcpy(blob.data(), &kh, sizeof kh);
-        memcpy(blob.data() + sizeof kh, offs[j].data(), (size_t)(nk + 1) * 8);
-        if (!pay[j].empty()) memcpy(blob.data() + sizeof kh + (nk + 1) * 8, pay[j].data(), pay[j].size());
-        const int rc = restore_any(h->kids[j], blob.data(), (int64_t)blob.size(), true);
-        if (rc) return kid_rc(h, h->kids[j], rc);
+        blobs[j] = w[j].finish(kh);
     }
-    if (dry) return GW_OK;
-    for (int64_t j = 0; j < J; ++j) {  // checked above: only a device error can fail here
-        const int rc = restore_any(h->kids[j], blobs[j].data(), (int64_t)blobs[j].size(), false);
-        if (rc) return kid_rc(h, h->kids[j], rc);
-    }
-    return GW_OK;
+    const int rc = restore_parts(h, h->kids, blobs, true);
+    return rc || dry ? rc : restore_parts(h, h->kids, blobs, false);
 }
 
 #define HIPCHECK_H(h, x)                                                                                  \
@@ -4289,64 +4077,48 @@ static int comp_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
 // The reference keeps one reduced Tuple per (key, window): the window's first element with
 // the aggregated field replaced (HeapReducingState.java:90-97, SumAggregator /
 // ComparableAggregator).  The blob holds exactly that per entry: (window, key, [hash],
-// aggregate, payload of the first element) with flags |= kSnapFirstElement, and kids[0]'s
+// aggregate, payload of the first element) with flags |= snap::kFirstElement, and kids[0]'s
 // timers.  A restore gives the restored first elements new arrival sequences: their payloads
 // go to the log, kids[1] gets (window, key, new sequence) entries.
 // minBy / maxBy handles hold the same entries: the element's payload comes from the log
 // (fe_by_select over the entries' (key, window, MIN / MAX)) instead of kids[1]'s sequence.
 static int fe_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
-    gw_handle *A = h->kids[0], *B = h->fe_by ? h->kids[0] : h->kids[1];
-    std::vector<uint8_t> ba, bb;
-    for (auto pr : {std::make_pair(A, &ba), std::make_pair(B, &bb)}) {
-        if (h->fe_by && pr.second == &bb) {
-            bb = ba;
-            break;
-        }
-        int64_t l = 0;
-        int rc = gw_snapshot(pr.first, kg_lo, kg_hi, nullptr, 0, &l);
-        if (rc) return kid_rc(h, pr.first, rc);
-        pr.second->resize((size_t)l);
-        if ((rc = gw_snapshot(pr.first, kg_lo, kg_hi, pr.second->data(), l, &l))) return kid_rc(h, pr.first, rc);
-    }
-    SnapHdr ha, hb;
-    memcpy(&ha, ba.data(), sizeof ha);
-    memcpy(&hb, bb.data(), sizeof hb);
-    if (ha.version != 4 || hb.version != 4 || ha.flags != hb.flags)
+    gw_handle* A = h->kids[0];
+    std::vector<uint8_t> ba, bb;  // the operators' blobs (minBy / maxBy: one operator)
+    int rc = kid_snapshot(h, A, kg_lo, kg_hi, ba);
+    if (rc == GW_OK && !h->fe_by) rc = kid_snapshot(h, h->kids[1], kg_lo, kg_hi, bb);
+    if (rc) return rc;
+    snap::Header ha, hb;
+    snap::Cursor ca, cb;
+    if (snap::open(ba.data(), (int64_t)ba.size(), 4, 4, ha, ca) ||
+        (!h->fe_by && (snap::open(bb.data(), (int64_t)bb.size(), 4, 4, hb, cb) || ha.flags != hb.flags)))
         return h->fail(GW_E_STATE, "first-element snapshot: the operators' blobs differ");
-    const int64_t nk = (int64_t)kg_hi - kg_lo + 1, hdr = (int64_t)sizeof(SnapHdr) + (nk + 1) * 8;
-    const int kb = (ha.flags & kSnapKeyHashes) ? 4 : 0;
-    const int64_t ea = 24 + kb + A->acc_bytes(), eb = 24 + kb + 8;  // B: MIN_I64 of the sequence
-    // pass 1: the sequences of every entry's first element, in entry order
+    // pass 1: kids[0]'s entries and timers (with their counts at each key group's end), and
+    // the sequences of every entry's first element, in entry order
+    std::vector<const uint8_t*> sa, ta, sb;
+    std::vector<std::pair<size_t, size_t>> ends;
+    std::vector<size_t> ends_b;
+    snap::Err bad = snap::walk_windows(
+        ha, ca, [&](const uint8_t* p) { sa.push_back(p); }, snap::NoSets{}, [&](const uint8_t* t) { ta.push_back(t); },
+        [&] { ends.push_back({sa.size(), ta.size()}); });
+    if (!bad && !h->fe_by)
+        bad = snap::walk_windows(
+            hb, cb, [&](const uint8_t* p) { sb.push_back(p); }, snap::NoSets{}, [](const uint8_t*) {},
+            [&] { ends_b.push_back(sb.size()); });
+    if (bad) return h->fail(bad);
+    const int64_t acc_at = snap::state_acc_at(ha), ea = snap::state_entry_bytes(ha);
     std::vector<int64_t> seqs, by_key, by_start, by_res;
-    struct Sec { const uint8_t *sa, *sb, *ta; int32_t n, t; };
-    std::vector<Sec> secs((size_t)nk);
-    for (int64_t g = 0; g < nk; ++g) {
-        int64_t oa, ob;
-        memcpy(&oa, ba.data() + sizeof(SnapHdr) + g * 8, 8);
-        memcpy(&ob, bb.data() + sizeof(SnapHdr) + g * 8, 8);
-        const uint8_t* pa = ba.data() + hdr + oa;
-        const uint8_t* pb = bb.data() + hdr + ob;
-        Sec sc{};
-        sc.n = gw_handle::rd32(pa);
-        if (gw_handle::rd32(pb) != sc.n) return h->fail(GW_E_STATE, "first-element snapshot: entries differ");
-        sc.sa = pa + 4;
-        sc.sb = pb + 4;
-        for (int32_t i = 0; i < sc.n; ++i) {
-            const uint8_t* xa = sc.sa + i * ea;
-            const uint8_t* xb = sc.sb + i * eb;
-            if (memcmp(xa, xb, 24 + kb) != 0) return h->fail(GW_E_STATE, "first-element snapshot: entries differ");
-            if (h->fe_by) {  // (start, end, key, [hash], MIN / MAX)
-                by_start.push_back(gw_handle::rd64(xa));
-                by_key.push_back(gw_handle::rd64(xa + 16));
-                by_res.push_back(gw_handle::rd64(xa + 24 + kb));
-            } else {
-                seqs.push_back(gw_handle::rd64(xb + 24 + kb));
-            }
+    for (size_t g = 0; g < ends_b.size(); ++g)
+        if (ends_b[g] != ends[g].first) return h->fail(GW_E_STATE, "first-element snapshot: entries differ");
+    for (size_t i = 0; i < sa.size(); ++i) {
+        if (h->fe_by) {  // (start, end, key, [hash], MIN / MAX)
+            by_start.push_back(snap::state_start(sa[i]));
+            by_key.push_back(snap::state_key(sa[i]));
+            by_res.push_back(snap::get64(sa[i] + acc_at));
+        } else {  // kids[1]: MIN_I64 of the sequence
+            if (memcmp(sa[i], sb[i], (size_t)acc_at) != 0) return h->fail(GW_E_STATE, "first-element snapshot: entries differ");
+            seqs.push_back(snap::get64(sb[i] + acc_at));
         }
-        sc.ta = sc.sa + sc.n * ea + 4;  // past the (empty) merging window set
-        sc.t = gw_handle::rd32(sc.ta);
-        sc.ta += 4;
-        secs[g] = sc;
     }
     std::vector<int64_t> pays(h->fe_by ? by_key.size() : seqs.size());
     if (h->fe_by && !by_key.empty()) {
@@ -4376,117 +4148,86 @@ static int fe_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, in
         if (e != hipSuccess) return h->fail(GW_E_DEVICE, "first-element snapshot: %s", hipGetErrorString(e));
     }
     // pass 2: the blob
-    std::vector<uint8_t> pay;
-    std::vector<int64_t> offs(nk + 1, 0);
-    size_t q = 0;
-    for (int64_t g = 0; g < nk; ++g) {
-        const Sec& sc = secs[g];
-        offs[g] = (int64_t)pay.size();
-        gw_handle::be32(pay, sc.n);
-        for (int32_t i = 0; i < sc.n; ++i) {
-            const uint8_t* xa = sc.sa + i * ea;
-            pay.insert(pay.end(), xa, xa + ea);
-            gw_handle::be64(pay, pays[q++]);
+    snap::Writer w;
+    size_t i = 0, t = 0;
+    for (const auto& end : ends) {
+        w.begin_group();
+        w.count((int32_t)(end.first - i));
+        for (; i < end.first; ++i) {
+            w.bytes(sa[i], ea);
+            snap::put64(w.pay, pays[i]);
         }
-        gw_handle::be32(pay, 0);
-        gw_handle::be32(pay, sc.t);
-        pay.insert(pay.end(), sc.ta, sc.ta + (size_t)sc.t * 32);
+        w.count(0);
+        w.count((int32_t)(end.second - t));
+        for (; t < end.second; ++t) w.bytes(ta[t], snap::kTimerBytes);
     }
-    offs[nk] = (int64_t)pay.size();
-    *len = hdr + (int64_t)pay.size();
-    if (!buf) return GW_OK;
-    if (cap < *len) return h->fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)*len);
-    SnapHdr hd = ha;
-    hd.agg = h->cfg.agg;
-    hd.flags |= kSnapFirstElement;
-    hd.entries = (int64_t)pay.size();
-    char* out = (char*)buf;
-    memcpy(out, &hd, sizeof hd);
-    memcpy(out + sizeof hd, offs.data(), (size_t)(nk + 1) * 8);
-    if (!pay.empty()) memcpy(out + hdr, pay.data(), pay.size());
-    return GW_OK;
+    ha.agg = h->cfg.agg;
+    ha.flags |= snap::kFirstElement;
+    return h->finish_blob(w, ha, buf, cap, len);
 }
 
 static int fe_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
-    if (!buf || len < (int64_t)sizeof(SnapHdr)) return h->fail(GW_E_INVALID, "snapshot blob too short");
-    SnapHdr hd;
-    memcpy(&hd, buf, sizeof hd);
-    if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version != 4 || !(hd.flags & kSnapFirstElement) || hd.agg != h->cfg.agg)
+    snap::Header hd;
+    snap::Cursor c;
+    snap::Err bad = snap::header(buf, len, 1, snap::kMaxVersion, hd);
+    if (bad) return h->fail(bad);
+    if (hd.version != 4 || !(hd.flags & snap::kFirstElement) || hd.agg != h->cfg.agg)
         return h->fail(GW_E_INVALID, "not a first-element snapshot of this aggregate");
-    gw_handle *A = h->kids[0], *B = h->fe_by ? nullptr : h->kids[1];
-    const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1, hdr = (int64_t)sizeof hd + (nk + 1) * 8;
-    if (nk <= 0 || hd.entries < 0 || len < hdr || hd.entries > len - hdr)
-        return h->fail(GW_E_INVALID, "truncated snapshot blob");
+    if ((bad = snap::payload(buf, len, hd, c))) return h->fail(bad);
+    // the two operators' blobs (minBy / maxBy: one): kids[0] gets the entries without their
+    // payloads, kids[1] (window, key, new sequence); both get the timers
+    std::vector<gw_handle*> ops(h->kids.begin(), h->kids.begin() + (h->fe_by ? 1 : 2));
     std::vector<int64_t> by_cols[3];  // minBy / maxBy: the restored elements' key, window start, field
-    const int kb = (hd.flags & kSnapKeyHashes) ? 4 : 0;
-    const int64_t ea = 24 + kb + A->acc_bytes(), ef = ea + 8;
-    const uint8_t* p = (const uint8_t*)buf + hdr;
-    const uint8_t* end = p + hd.entries;
-    std::vector<uint8_t> pa, pb;
-    std::vector<int64_t> oa(nk + 1), ob(nk + 1), pays;
+    const int64_t acc_at = snap::state_acc_at(hd), ea = snap::state_payload_at(hd);
+    snap::Writer w[2];
+    std::vector<uint8_t> st[2], tm;  // of the current key group
+    std::vector<int64_t> pays;
+    int32_t n = 0;
     int64_t max_end = INT64_MIN;
     const int64_t seq0 = h->fe_seq;
-    for (int64_t g = 0; g < nk; ++g) {
-        oa[g] = (int64_t)pa.size();
-        ob[g] = (int64_t)pb.size();
-        if (end - p < 4) return h->fail(GW_E_INVALID, "truncated snapshot blob");
-        const int32_t n = gw_handle::rd32(p);
-        p += 4;
-        if (n < 0 || (int64_t)n * ef + 8 > end - p) return h->fail(GW_E_INVALID, "truncated snapshot blob");
-        gw_handle::be32(pa, n);
-        gw_handle::be32(pb, n);
-        for (int32_t i = 0; i < n; ++i, p += ef) {
-            pa.insert(pa.end(), p, p + ea);
-            pb.insert(pb.end(), p, p + 24 + kb);
-            gw_handle::be64(pb, seq0 + (int64_t)pays.size());  // the restored first element's new sequence
-            pays.push_back(gw_handle::rd64(p + ea));
-            max_end = std::max(max_end, gw_handle::rd64(p + 8));
+    bad = snap::walk_windows(
+        hd, c,
+        [&](const uint8_t* p) {
+            st[0].insert(st[0].end(), p, p + ea);
+            st[1].insert(st[1].end(), p, p + acc_at);
+            snap::put64(st[1], seq0 + (int64_t)pays.size());  // the restored first element's new sequence
+            pays.push_back(snap::get64(p + ea));
+            max_end = std::max(max_end, snap::state_end(p));
+            n++;
             if (h->fe_by) {
-                by_cols[0].push_back(gw_handle::rd64(p + 16));
-                by_cols[1].push_back(gw_handle::rd64(p));
-                by_cols[2].push_back(gw_handle::rd64(p + 24 + kb));
+                by_cols[0].push_back(snap::state_key(p));
+                by_cols[1].push_back(snap::state_start(p));
+                by_cols[2].push_back(snap::get64(p + acc_at));
             }
-        }
-        if (gw_handle::rd32(p) != 0) return h->fail(GW_E_INVALID, "merging window set in a first-element snapshot");
-        p += 4;
-        const int32_t t = gw_handle::rd32(p);
-        p += 4;
-        if (t < 0 || (int64_t)t * 32 > end - p) return h->fail(GW_E_INVALID, "truncated snapshot blob");
-        for (std::vector<uint8_t>* v : {&pa, &pb}) {
-            gw_handle::be32(*v, 0);
-            gw_handle::be32(*v, t);
-            v->insert(v->end(), p, p + (size_t)t * 32);
-        }
-        p += (size_t)t * 32;
+        },
+        snap::NoSets{"merging window set in a first-element snapshot"},
+        [&](const uint8_t* t) { tm.insert(tm.end(), t, t + snap::kTimerBytes); },
+        [&] {
+            for (int o = 0; o < 2; ++o) {
+                w[o].begin_group();
+                w[o].section(n, st[o]);
+                w[o].section(0, {});
+                w[o].section((int32_t)(tm.size() / snap::kTimerBytes), tm);
+                st[o].clear();
+            }
+            tm.clear();
+            n = 0;
+        });
+    if (bad) return h->fail(bad);
+    std::vector<std::vector<uint8_t>> blobs(ops.size());
+    for (size_t o = 0; o < ops.size(); ++o) {
+        snap::Header kh = hd;
+        kh.flags &= ~snap::kFirstElement;
+        kh.agg = o ? GW_MIN_I64 : h->cfg.agg;
+        blobs[o] = w[o].finish(kh);
     }
-    if (p != end) return h->fail(GW_E_INVALID, "snapshot blob has trailing bytes");
-    oa[nk] = (int64_t)pa.size();
-    ob[nk] = (int64_t)pb.size();
-    // the two operators' blobs, each checked (a dry restore: header, windows, counts, key
-    // hashes, restore before processing) before the log or any operator changes
-    std::vector<uint8_t> blobs[2];
-    for (int w = 0; w < (h->fe_by ? 1 : 2); ++w) {
-        std::vector<uint8_t>& pl = w ? pb : pa;
-        std::vector<int64_t>& of = w ? ob : oa;
-        SnapHdr kh = hd;
-        kh.flags &= ~kSnapFirstElement;
-        kh.agg = w ? GW_MIN_I64 : h->cfg.agg;
-        kh.entries = (int64_t)pl.size();
-        std::vector<uint8_t>& blob = blobs[w];
-        blob.resize(sizeof kh + (size_t)(nk + 1) * 8 + pl.size());
-        memcpy(blob.data(), &kh, sizeof kh);
-        memcpy(blob.data() + sizeof kh, of.data(), (size_t)(nk + 1) * 8);
-        if (!pl.empty()) memcpy(blob.data() + sizeof kh + (nk + 1) * 8, pl.data(), pl.size());
-        gw_handle* kid = w ? B : A;
-        const int rc = restore_any(kid, blob.data(), (int64_t)blob.size(), true);
-        if (rc) return kid_rc(h, kid, rc);
-    }
-    if (dry) return GW_OK;
+    // checked before the log or any operator changes
+    int rc = restore_parts(h, ops, blobs, true);
+    if (rc || dry) return rc;
     // the payloads enter the log as one batch released once every restored window is cleaned
     const int64_t m = (int64_t)pays.size();
     if (m) {
-        int rc = fe_log_reserve(h, m);
-        if (rc) return rc;
+        if ((rc = fe_log_reserve(h, m))) return rc;
         int64_t* d = nullptr;
         HIPCHECK_H(h, hipMalloc((void**)&d, (size_t)m * 8 * h->fe_cols));
         hipError_t e = hipMemcpy(d, pays.data(), (size_t)m * 8, hipMemcpyHostToDevice);
@@ -4502,12 +4243,7 @@ static int fe_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
         // released like a batch whose records reach the latest restored window: maxTs + size - 1 = its end - 1
         h->fe_batches.push_back({h->fe_seq, 0, max_end - h->cfg.size, true});
     }
-    for (int w = 0; w < (h->fe_by ? 1 : 2); ++w) {  // checked above: only a device error can fail here
-        gw_handle* kid = w ? B : A;
-        const int rc = restore_any(kid, blobs[w].data(), (int64_t)blobs[w].size(), false);
-        if (rc) return kid_rc(h, kid, rc);
-    }
-    return GW_OK;
+    return restore_parts(h, ops, blobs, false);
 }
 
 int gw_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
@@ -4534,48 +4270,22 @@ int gw_restore(gw_handle* h, const void* buf, int64_t len) {
     return restore_any(h, buf, len, false);
 }
 
-// The blob layout is gw_handle::SnapHeader (96 bytes: kg_lo at 60, kg_hi at 64, reserved at
-// 68, entries at 88), kg_offsets[kg_hi - kg_lo + 2], then the entries; an entry is 32 bytes in
-// version 1 and `reserved` int64 words in every later version.
+// The blob layout is snap::Header (96 bytes: kg_lo at 60, kg_hi at 64, reserved at 68,
+// entries at 88), kg_offsets[kg_hi - kg_lo + 2], then the entries; an entry is 32 bytes in
+// version 1, `reserved` int64 words in versions 2 and 3 and one byte in version 4.
 int gw_snapshot_slice(const void* blob, int64_t len, int32_t kg, void* out, int64_t cap, int64_t* out_len) {
-    typedef gw_handle::SnapHeader H;
-    static_assert(sizeof(H) == 96, "snapshot header layout");
-    if (!blob || !out_len || len < (int64_t)sizeof(H)) { g_create_error = "snapshot blob too short"; return GW_E_INVALID; }
-    H hd;
-    memcpy(&hd, blob, sizeof hd);
-    if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version < 1 || hd.version > kSnapMaxVersion) {
-        g_create_error = "not a gpuwin snapshot";
-        return GW_E_INVALID;
-    }
-    const int64_t ew = hd.version == 1 ? 32 : hd.version >= 4 ? 1 : (int64_t)hd.reserved * 8;  // v4: bytes
-    const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-    if (ew <= 0 || nk <= 0 || hd.entries < 0 || len < (int64_t)sizeof hd + (nk + 1) * 8 ||
-        hd.entries > (len - (int64_t)sizeof hd - (nk + 1) * 8) / ew) {
-        g_create_error = "truncated snapshot blob";
-        return GW_E_INVALID;
-    }
-    if (kg < hd.kg_lo || kg > hd.kg_hi) {
-        g_create_error = "key group outside the blob's key-group range";
-        return GW_E_INVALID;
-    }
-    const char* b = (const char*)blob;
-    int64_t o0, o1;
-    memcpy(&o0, b + sizeof hd + (kg - hd.kg_lo) * 8, 8);
-    memcpy(&o1, b + sizeof hd + (kg - hd.kg_lo + 1) * 8, 8);
-    if (o0 < 0 || o1 < o0 || o1 > hd.entries) { g_create_error = "corrupt snapshot offsets"; return GW_E_INVALID; }
-    const int64_t n = o1 - o0;
-    const int64_t need = (int64_t)sizeof hd + 16 + n * ew;
-    *out_len = need;
-    if (!out) return GW_OK;
-    if (cap < need) { g_create_error = "slice buffer too small"; return GW_E_OUTPUT_FULL; }
-    H oh = hd;
-    oh.kg_lo = oh.kg_hi = kg;
-    oh.entries = n;
-    char* o = (char*)out;
-    memcpy(o, &oh, sizeof oh);
-    const int64_t offs[2] = {0, n};
-    memcpy(o + sizeof oh, offs, 16);
-    if (n) memcpy(o + sizeof oh + 16, b + sizeof hd + (nk + 1) * 8 + o0 * ew, (size_t)(n * ew));
+    snap::Header hd;
+    snap::Cursor c, part;
+    snap::Err e = out_len ? snap::open(blob, len, 1, snap::kMaxVersion, hd, c) : snap::invalid("snapshot blob too short");
+    if (!e && (kg < hd.kg_lo || kg > hd.kg_hi)) e = snap::invalid("key group outside the blob's key-group range");
+    if (!e) e = snap::group(blob, hd, kg - hd.kg_lo, part);
+    if (e) { g_create_error = e.reason; return e.code; }
+    snap::Writer w;
+    w.begin_group();
+    const int64_t n = part.left();
+    w.bytes(part.take(n), n);
+    hd.kg_lo = hd.kg_hi = kg;
+    if (w.finish(hd, out, cap, out_len)) { g_create_error = "slice buffer too small"; return GW_E_OUTPUT_FULL; }
     return GW_OK;
 }
 
@@ -4584,105 +4294,42 @@ extern "C++" {
 // version 2-4 blob; false for a corrupt blob.
 template <class F>
 static bool blob_keys(const uint8_t* b, int64_t len, F&& f) {
-    typedef gw_handle::SnapHeader H;
-    H hd;
-    if (!b || len < (int64_t)sizeof hd) return false;
-    memcpy(&hd, b, sizeof hd);
-    if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version < 2 || hd.version > kSnapMaxVersion) return false;
-    const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1;
-    const int64_t pay0 = (int64_t)sizeof hd + (nk + 1) * 8;
-    if (nk <= 0 || hd.entries < 0 || len < pay0) return false;
-    const uint8_t* p = b + pay0;
-    if (hd.version < 4) {  // fixed entries of `reserved` int64 words, key first
-        const int64_t ew = (int64_t)hd.reserved * 8;
-        if (ew <= 0 || hd.entries > (len - pay0) / ew) return false;
-        for (int64_t i = 0; i < hd.entries; ++i) f(p + i * ew, false);
+    snap::Header hd;
+    snap::Cursor c;
+    if (snap::open(b, len, 2, snap::kMaxVersion, hd, c)) return false;
+    if (hd.version < 4) {  // fixed entries, key first
+        while (const uint8_t* p = c.take(snap::entry_unit(hd))) f(p, false);
         return true;
     }
-    if (hd.entries > len - pay0) return false;
-    const uint8_t* end = p + hd.entries;
-    const int64_t ab = hd.agg == GW_SUM_I32 ? 4 : (hd.agg == GW_AVG_I64 || hd.agg == GW_AVG_F64) ? 16 : 8;
-    if (hd.assigner == GW_COUNT_TUMBLING) {  // (GlobalWindow byte, key, [hash,] state) and (byte, key, [hash,] count)
-        const int64_t hb = (hd.flags & kSnapKeyHashes) ? 4 : 0;
-        for (int64_t g = 0; g < nk; ++g) {
-            for (int sec = 0; sec < 2; ++sec) {
-                const int64_t eb = 9 + hb + (sec ? 8 : ab);
-                if (end - p < 4) return false;
-                const int32_t n = gw_handle::rd32(p);
-                p += 4;
-                if (n < 0 || (int64_t)n * eb > end - p) return false;
-                for (int32_t i = 0; i < n; ++i, p += eb) f(p + 1, true);
-            }
-            if (end - p < 4 || gw_handle::rd32(p) != 0) return false;
-            p += 4;
-        }
-        return p == end;
+    if (hd.assigner == GW_COUNT_TUMBLING) {
+        auto keys = [&](snap::Entries s) {
+            for (int32_t i = 0; i < s.n; ++i) f(s[i] + snap::kCountKeyAt, true);
+        };
+        return !snap::walk_count_windows(hd, c, keys, keys);
     }
-    const int64_t eb = 24 + ((hd.flags & kSnapKeyHashes) ? 4 : 0) + ((hd.flags & kSnapFirstElement) ? 8 : 0) + ab;
-    for (int64_t g = 0; g < nk; ++g) {
-        if (end - p < 4) return false;
-        const int32_t n = gw_handle::rd32(p);
-        p += 4;
-        if (n < 0 || (int64_t)n * eb + 4 > end - p) return false;
-        for (int32_t i = 0; i < n; ++i, p += eb) f(p + 16, true);
-        const int32_t m = gw_handle::rd32(p);
-        p += 4;
-        if (m < 0) return false;
-        const int64_t mh = 12 + ((hd.flags & kSnapKeyHashes) ? 4 : 0);
-        for (int32_t i = 0; i < m; ++i) {  // merging window sets: (key, [be32 hash,] be32 c, c x 32 B)
-            if (end - p < mh) return false;
-            const int32_t c = gw_handle::rd32(p + mh - 4);
-            if (c < 0 || (int64_t)c * 32 > end - p - mh) return false;
-            f(p, true);
-            p += mh + (int64_t)c * 32;
-        }
-        if (end - p < 4) return false;
-        const int32_t t = gw_handle::rd32(p);
-        p += 4;
-        if (t < 0 || (int64_t)t * 32 > end - p) return false;
-        for (int32_t i = 0; i < t; ++i, p += 32) f(p + 8, true);
-    }
-    return p == end;
+    return !snap::walk_windows(
+        hd, c, [&](const uint8_t* p) { f(p + snap::kStateKeyAt, true); },
+        [&](const uint8_t* head, int32_t, const uint8_t*) { f(head, true); },
+        [&](const uint8_t* t) { f(t + snap::kTimerKeyAt, true); }, [] {});
 }
 
 static int64_t key_at(const uint8_t* p, bool be) {
-    if (be) return gw_handle::rd64(p);
+    if (be) return snap::get64(p);
     int64_t k;
     memcpy(&k, p, 8);
     return k;
 }
 
-}  // extern "C++"
-
-extern "C++" {
 // Calls f(payload field, window end) for every entry of a first-element blob; false for a
 // corrupt blob or one without payloads.
 template <class F>
 static bool blob_payloads(const uint8_t* b, int64_t len, F&& f) {
-    typedef gw_handle::SnapHeader H;
-    H hd;
-    if (!b || len < (int64_t)sizeof hd) return false;
-    memcpy(&hd, b, sizeof hd);
-    if (memcmp(hd.magic, "GWS1", 4) != 0 || hd.version != 4 || !(hd.flags & kSnapFirstElement)) return false;
-    const int64_t acc = hd.agg == GW_SUM_I32 ? 4 : (hd.agg == GW_AVG_I64 || hd.agg == GW_AVG_F64) ? 16 : 8;
-    const int64_t at = 24 + ((hd.flags & kSnapKeyHashes) ? 4 : 0) + acc, eb = at + 8;
-    const int64_t nk = (int64_t)hd.kg_hi - hd.kg_lo + 1, pay0 = (int64_t)sizeof hd + (nk + 1) * 8;
-    if (nk <= 0 || hd.entries < 0 || len < pay0 || hd.entries > len - pay0) return false;
-    const uint8_t* p = b + pay0;
-    const uint8_t* end = p + hd.entries;
-    for (int64_t g = 0; g < nk; ++g) {
-        if (end - p < 4) return false;
-        const int32_t n = gw_handle::rd32(p);
-        p += 4;
-        if (n < 0 || (int64_t)n * eb + 8 > end - p) return false;
-        for (int32_t i = 0; i < n; ++i, p += eb) f(p + at, gw_handle::rd64(p + 8));
-        p += 4;  // (empty) merging window set
-        const int32_t t = gw_handle::rd32(p);
-        p += 4;
-        if (t < 0 || (int64_t)t * 32 > end - p) return false;
-        p += (int64_t)t * 32;
-    }
-    return p == end;
+    snap::Header hd;
+    snap::Cursor c;
+    if (snap::open(b, len, 4, 4, hd, c) || !(hd.flags & snap::kFirstElement)) return false;
+    const int64_t at = snap::state_payload_at(hd);
+    return !snap::walk_windows(
+        hd, c, [&](const uint8_t* p) { f(p + at, snap::state_end(p)); }, snap::NoSets{}, [](const uint8_t*) {}, [] {});
 }
 
 }  // extern "C++"
@@ -4693,7 +4340,7 @@ int gw_snapshot_payloads(const void* blob, int64_t len, int64_t* payloads, int64
     std::vector<int64_t> ps;
     int64_t mx = INT64_MIN;
     if (!blob_payloads((const uint8_t*)blob, len, [&](const uint8_t* p, int64_t e) {
-            ps.push_back(gw_handle::rd64(p));
+            ps.push_back(snap::get64(p));
             mx = std::max(mx, e);
         })) {
         g_create_error = "not a first-element snapshot blob";
@@ -4715,7 +4362,7 @@ int gw_snapshot_remap_payloads(void* blob, int64_t len, const int64_t* from, con
         if (from[i] <= from[i - 1]) { g_create_error = "remap payloads: from[] not ascending"; return GW_E_INVALID; }
     const bool ok = blob_payloads((const uint8_t*)blob, len, [&](const uint8_t* cp, int64_t) {
         uint8_t* p = const_cast<uint8_t*>(cp);
-        const int64_t v = gw_handle::rd64(p);
+        const int64_t v = snap::get64(p);
         const int64_t* it = std::lower_bound(from, from + n, v);
         if (it == from + n || *it != v) return;
         const int64_t w = to[it - from];

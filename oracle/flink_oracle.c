@@ -1270,7 +1270,7 @@ int wo_set_key_hashes(wo_op* op, int64_t n, const int64_t* key, const int32_t* h
     return GW_OK;
 }
 
-/* The 96-byte blob header (include/gpuwin.h gw_snapshot, gw_runtime.cpp SnapHeader). */
+/* The 96-byte blob header (include/gpuwin.h gw_snapshot, gw_snapshot.h snap::Header). */
 static void snap_header(const wo_op* op, int32_t kg_lo, int32_t kg_hi, int hashed, int64_t payload, uint8_t* h) {
     memset(h, 0, 96);
     memcpy(h, "GWS1", 4);

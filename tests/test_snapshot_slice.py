@@ -10,7 +10,7 @@ import pytest
 
 from flink_amd import _native as N
 
-HDR = struct.Struct("<4sIii5q4i3q")  # include/gpuwin.h gw_snapshot / gw_handle::SnapHeader
+HDR = struct.Struct("<4sIii5q4i3q")  # include/gpuwin.h gw_snapshot / gw_snapshot.h snap::Header
 assert HDR.size == 96
 
 
