@@ -33,6 +33,10 @@ constexpr uint32_t kOsLocal = 1u << 30, kOsIncl = 2u << 30, kOsMask = (1u << 30)
 constexpr int kOsMaxBins = 512;
 // Experiment builds only (flink_amd.build --define GW_SORT_EXP=n --out ...), results discarded:
 // 1 no look-back, 2 no ranking, 4 no write-out.  The product library is built with 0.
+// 1 keeps its writes in bounds in a sort of one pass only (tiles overwrite each other inside their
+// bins): the histogram is taken once, from the input, and a later pass would place what the
+// broken pass left -- duplicates and unwritten words -- by counts that no longer match it, up to
+// a tile beyond the end of the output.
 #ifndef GW_SORT_EXP
 #define GW_SORT_EXP 0
 #endif

@@ -11,6 +11,7 @@ import pytest
 from flink_amd import _native as N
 from flink_amd import windowing as W
 from tests.harness import load_golden
+from tests.sort_native import sort_entry_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -106,14 +107,8 @@ def test_grouping_sort_refuses_counts_beyond_its_prefix_field():
     returns hipErrorInvalidValue for n >= 2^30 before any launch (host-side guard; the session,
     count-window and re-fire callers split or refuse such batches), instead of spilling the
     prefix into the flag bits."""
-    L = N.lib()
-    p = ctypes.c_void_p
-    for sym in ("_ZN2gw14sort_pairs_u32EPjS0_S0_S0_liiPvP12ihipStream_tPib",
-                "_ZN2gw14sort_pairs_u64EPmPjS0_S1_liiPvP12ihipStream_tPib"):
-        f = getattr(L, sym)
-        f.restype = ctypes.c_int
-        f.argtypes = [p, p, p, p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, p, p, ctypes.POINTER(ctypes.c_int),
-                      ctypes.c_bool]
+    S = sort_entry_points()
+    for f in (S.sort_pairs_u32, S.sort_pairs_u64):
         alt = ctypes.c_int(-1)
         for n in (1 << 30, (1 << 31) - 1, 1 << 40):
             assert f(None, None, None, None, n, 0, 26, None, None, ctypes.byref(alt), False) == 1  # hipErrorInvalidValue
