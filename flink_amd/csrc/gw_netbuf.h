@@ -20,6 +20,10 @@ struct NbLayout {
     int32_t val_type;  // its type code ('J', 'D', ...), 0 = none (COUNT)
 };
 
+// corrupt / unsupported: 0 = none, otherwise nb_error_rank of the earliest byte position that
+// raised it (larger = earlier).  The sequential reader fails on the stream's first bad element;
+// the chunks behind it may still decode (from a later chunk with a unique exit) and raise errors
+// of their own, so of the two the one with the larger rank is the stream's (nb_corrupt_first).
 struct NbStatus {
     unsigned long long corrupt;      // unknown tag / length that does not match the element
     unsigned long long unsupported;  // an element longer than GW_MAX_ELEMENT
@@ -30,6 +34,12 @@ struct NbStatus {
     unsigned long long walkback;     // chunk steps k_nb_resolve walked back over non-converged chunks
     unsigned long long fallback;     // chunks whose candidates disagreed after the sync window
 };
+
+__host__ __device__ inline unsigned long long nb_error_rank(int64_t pos) {
+    return (1ull << 62) - (unsigned long long)pos;
+}
+// corrupt is the stream's first error (a chunk-granular corrupt rank ties towards corrupt)
+inline bool nb_corrupt_first(const NbStatus& st) { return st.corrupt && st.corrupt >= st.unsupported; }
 
 inline int nb_field_width(char t) {
     switch (t) {

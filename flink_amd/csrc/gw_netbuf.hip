@@ -392,7 +392,7 @@ __global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(int64_t nbytes, int
             if (p >= nbytes) {
                 // the chain ended exactly at the end of the bytes: nothing starts here
             } else if (lane < 0 || lane >= NL) {
-                atomicOr(&st->corrupt, 1ull);
+                atomicMax(&st->corrupt, nb_error_rank(p));
             } else {
                 ent = p;
                 const int64_t ex = nb_exit_word<NL>(exits, sync, conv, c, lane);
@@ -406,8 +406,10 @@ __global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(int64_t nbytes, int
                     nw += (int)(tcnt[c] >> 16);
                 }
                 const int s = nb_state(ex);
-                if (s == kStDead) atomicOr(&st->corrupt, 1ull);
-                if (s == kStLong) atomicOr(&st->unsupported, 1ull);
+                // where the true chain stopped: the stream's first error is the one that counts,
+                // the chunks behind it may decode again from a later unique exit and raise others
+                if (s == kStDead) atomicMax(&st->corrupt, nb_error_rank(nb_pos(ex)));
+                if (s == kStLong) atomicMax(&st->unsupported, nb_error_rank(nb_pos(ex)));
                 if (s == kStTail) st->consumed = nb_pos(ex);  // at most one chunk of the chain stops early
                 if (s == kStNormal && nb_pos(ex) >= nbytes) st->consumed = nbytes;
             }
@@ -564,7 +566,7 @@ __global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t n
             if (m > kNbMaxElems) m = kNbMaxElems;
         }
         // more elements than valid ones of >= 6 bytes can make: lengths of 1 -> corrupt
-        if (lane == 0 && m == kNbMaxElems && pos < rend) atomicOr(&st->corrupt, 1ull);
+        if (lane == 0 && m == kNbMaxElems && pos < rend) atomicMax(&st->corrupt, nb_error_rank(base));
         if (lane == 0) nelem[w] = m;
     }
     __builtin_amdgcn_wave_barrier();
@@ -624,7 +626,7 @@ __global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t n
     bad = __ballot(bad != 0) != 0;  // one ballot each instead of a wave reduction
     full = __ballot(full != 0) != 0;
     if (lane == 0) {
-        if (bad) atomicOr(&st->corrupt, 1ull);
+        if (bad) atomicMax(&st->corrupt, nb_error_rank(base));
         if (full) atomicOr(&st->full, 1ull);
         if (skipped) atomicAdd(&st->skipped, skipped);
     }

@@ -3669,7 +3669,7 @@ static int nb_status_code(const NbStatus& st, std::string& why) {
 #ifdef GW_DEBUG_LOG  // experiment builds only
     fprintf(stderr, "gw netbuf: fallback %llu walkback %llu\n", st.fallback, st.walkback);
 #endif
-    if (st.corrupt) { why = "Corrupt stream: unknown tag or element length (StreamElementSerializer)"; return GW_E_INVALID; }
+    if (nb_corrupt_first(st)) { why = "Corrupt stream: unknown tag or element length (StreamElementSerializer)"; return GW_E_INVALID; }
     if (st.unsupported) { why = "stream element longer than GW_MAX_ELEMENT bytes"; return GW_E_UNSUPPORTED; }
     if (st.full) { why = "decoded records / watermarks exceed the output capacity"; return GW_E_OUTPUT_FULL; }
     return GW_OK;

@@ -11,6 +11,7 @@ import pytest
 from flink_amd import _native as N
 from flink_amd import windowing as W
 from tests.harness import load_golden
+from tests.netbuf_native import NbLayout, NbStatus, nb_entry_points
 from tests.sort_native import sort_entry_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,3 +114,16 @@ def test_grouping_sort_refuses_counts_beyond_its_prefix_field():
         for n in (1 << 30, (1 << 31) - 1, 1 << 40):
             assert f(None, None, None, None, n, 0, 26, None, None, ctypes.byref(alt), False) == 1  # hipErrorInvalidValue
             assert alt.value == 0
+
+
+def test_netbuf_decoder_entry_points_and_struct_sizes():
+    """The two C++ entry points tests/netbuf_native.py binds resolve, the scratch size is the
+    per-chunk sum gw_netbuf.hip lays out, and the ctypes mirrors have gw_netbuf.h's sizes
+    (NbLayout: 4 x int32; NbStatus: 9 x 8 bytes)."""
+    E = nb_entry_points()
+    assert E.launch_nb_decode is not None
+    assert E.nb_scratch_bytes(0) == 256
+    assert E.nb_scratch_bytes(1) == E.nb_scratch_bytes(1024) == 128 * 8 + 40 + 4 * 32 + 16 + 256
+    assert E.nb_scratch_bytes(1025) - E.nb_scratch_bytes(1024) == 128 * 8 + 40 + 4 * 32
+    assert ctypes.sizeof(NbLayout) == 16 and ctypes.sizeof(NbStatus) == 72
+    assert NbStatus.consumed.offset == 32 and NbStatus.fallback.offset == 64

@@ -62,8 +62,12 @@ def test_decode_matches_oracle(oracle_lib, types, kf, vf):
 
 
 def test_decode_payload_mimicking_length_words(oracle_lib):
-    # payload bytes that read as valid element lengths keep wrong candidate entries alive
-    # across whole chunks: the resolve step must follow the true chain back
+    # payload words that read as plausible element lengths.  The walk kills a candidate whose
+    # length does not fit its tag, so of these four only (25 << 32) | 25 survives a step (as
+    # "length 25, tag 0"), and the next record kills it: many chunks leave the sync window
+    # undecided and walk on to their end (fallback), hardly any stays non-converged.  Chains
+    # that stay wrong over whole runs of chunks, and the resolve step's walk back over them, are
+    # tests/test_gpu_netbuf_paths.py's
     vals = [(25 << 32) | 25, (13 << 32) | 9, 0x0000001d0000001d, (1 << 32) | 2]
     parts = []
     for i in range(30000):

@@ -57,6 +57,80 @@ def py_decode(data, types, key_field, value_field):
     return recs, wms, pos
 
 
+class Decoded:
+    """py_decode_full's result: the status code, the element list and the columns of everything
+    decoded before the stream ended or failed.  A prefix of n bytes of a stream that decodes with
+    status 0 holds the elements that end at or before n and nothing else, so what its decode must
+    give follows from the element ends alone (prefix)."""
+
+    def __init__(self, rc, starts, ends, kinds, recs, wms):
+        self.rc = rc
+        self.starts, self.ends = np.asarray(starts, np.int64), np.asarray(ends, np.int64)
+        kinds = np.asarray(kinds, np.int64)  # 0 record, 1 watermark, 2 skipped
+        self.cum = np.zeros((3, len(kinds) + 1), np.int64)
+        for k in range(3):
+            self.cum[k, 1:] = np.cumsum(kinds == k)
+        r = np.asarray(recs, np.int64).reshape(-1, 3)
+        w = np.asarray(wms, np.int64).reshape(-1, 2)
+        self.key, self.ts, self.val = (np.ascontiguousarray(r[:, i]) for i in range(3))
+        self.wm_pos, self.wm_val = (np.ascontiguousarray(w[:, i]) for i in range(2))
+        self.records, self.watermarks, self.skipped = (int(self.cum[k, -1]) for k in range(3))
+        self.consumed = int(self.ends[-1]) if len(self.ends) else 0
+
+    def prefix(self, n):
+        """(records, watermarks, skipped, consumed) of the first n bytes."""
+        assert self.rc == 0 or n <= self.consumed
+        m = int(np.searchsorted(self.ends, n, side="right"))
+        return int(self.cum[0, m]), int(self.cum[1, m]), int(self.cum[2, m]), int(self.ends[m - 1]) if m else 0
+
+
+def py_decode_full(data, types, key_field, value_field):
+    """py_decode with the skipped count, the element starts and the oracle's status code for a
+    stream that fails, in the order the oracle checks (oracle/flink_oracle.c wo_decode_stream): a
+    length below 1 is corrupt (-1), an element beyond GW_MAX_ELEMENT = 128 bytes is unsupported
+    (-2), an element that spans past the end stops the decode, then an unknown tag or a length
+    that does not fit its tag is corrupt (-1).  -> Decoded."""
+    offs = np.cumsum([0] + [WIDTH[t] for t in types])
+    vbytes = int(offs[-1])
+    fits = {0: 9 + vbytes, 1: 1 + vbytes, 2: 9, 3: 29, 4: 5, 5: 2, 6: 13}
+    pos, rc, recs, wms, starts, ends, kinds = 0, 0, [], [], [], [], []
+    while pos + 4 <= len(data):
+        (ln,) = struct.unpack_from(">i", data, pos)
+        if ln < 1:
+            rc = -1
+            break
+        if ln + 4 > 128:
+            rc = -2
+            break
+        if pos + 4 + ln > len(data):
+            break
+        tag = data[pos + 4]
+        if fits.get(tag) != ln:
+            rc = -1
+            break
+        if tag in (0, 1):
+            hdr = 9 if tag == 0 else 1
+            ts = struct.unpack_from(">q", data, pos + 5)[0] if tag == 0 else LONG_MIN
+            v0 = pos + 4 + hdr
+            key = struct.unpack_from(">q", data, v0 + offs[key_field])[0]
+            val = 0
+            if value_field >= 0:
+                t = types[value_field]
+                x = struct.unpack_from(FMT[t], data, v0 + offs[value_field])[0]
+                val = struct.unpack("<q", struct.pack("<d", float(x)))[0] if t in "DF" else int(x)
+            recs.append((key, ts, val))
+            kinds.append(0)
+        elif tag in (2, 6):
+            wms.append((len(recs), struct.unpack_from(">q", data, pos + (5 if tag == 2 else 9))[0]))
+            kinds.append(1)
+        else:
+            kinds.append(2)
+        starts.append(pos)
+        pos += 4 + ln
+        ends.append(pos)
+    return Decoded(rc, starts, ends, kinds, recs, wms)
+
+
 def random_elements(rng, n, types, key_field, value_field, p_wm=0.05, p_other=0.05, p_nots=0.02):
     out, recs = [], []
     ts = 1000
