@@ -22,7 +22,8 @@ GW_E_NO_TIMESTAMP, GW_E_RANGE, GW_E_STATE = -6, -7, -8
 STAGE_VALUE, STAGE_KEY_HASH = 1, 2
 TOPN_MAX_N, TOPN_MAX_WINDOWS, TOPN_SMALLEST, TOPN_F64 = 64, 1024, 1, 2  # gpuwin.h GW_TOPN_*
 
-ASSIGNERS = {"tumbling": 0, "sliding": 1, "session": 2, "count_tumbling": 3, "count_sliding": 4}
+ASSIGNERS = {"tumbling": 0, "sliding": 1, "session": 2, "count_tumbling": 3, "count_sliding": 4,
+             "session_dynamic": 5}
 TRIGGERS = {"event_time": 0, "purging_event_time": 1}
 AGGS = {
     "count": 0, "sum_i64": 1, "sum_f64": 2, "min_i64": 3, "max_i64": 4,
@@ -60,6 +61,7 @@ EXPORTS = [
     "gw_select_lookup_device", "gw_top_n_device", "gw_top_n_rows", "gw_top_n_host",
     "gw_exchange_enable_packing", "gw_exchange_last_packed", "gw_exchange_plan_packed",
     "gw_exchange_set_unpack", "gw_exchange_last_words", "gw_ingest_packed_device",
+    "gw_ingest_gap", "gw_ingest_gap_device",
 ]
 EXCHANGE_ID_BYTES = 128
 EXCHANGE_RECV_SETS = 3  # gpuwin.h GW_EXCHANGE_RECV_SETS
@@ -155,6 +157,8 @@ def lib() -> ctypes.CDLL:
         "gw_abi_version": (c_int, []),
         "gw_ingest": (c_int, [p, i64, p, p, p, p]),
         "gw_ingest_device": (c_int, [p, i64, p, p, p, p, p]),
+        "gw_ingest_gap": (c_int, [p, i64, p, p, p, p, p]),
+        "gw_ingest_gap_device": (c_int, [p, i64, p, p, p, p, p, p]),
         "gw_advance_watermark": (c_int, [p, i64, P64]),
         "gw_flush": (c_int, [p]),
         "gw_snapshot": (c_int, [p, i32, i32, p, i64, P64]),

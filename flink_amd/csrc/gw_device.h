@@ -55,6 +55,7 @@ constexpr int kPubSeqWord = 3;
 #define GW_DF_NO_TS 1ull
 #define GW_DF_RANGE 2ull
 #define GW_DF_TABLE_FULL 4ull
+#define GW_DF_BAD_GAP 8ull  // dynamic-gap sessions: a record's gap is not positive
 
 __device__ __forceinline__ int64_t* slot_ptr(const TableView& t, int64_t idx) {
     return t.base + idx * (int64_t)t.stride_w;

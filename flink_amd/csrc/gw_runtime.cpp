@@ -39,6 +39,10 @@ thread_local std::string g_create_error;
 
 constexpr int64_t kMaxIngest = (int64_t)1 << 30;
 
+// Event-time session assigners: a constant gap, or one per element (the same state, blob
+// body and firing; only the element's window differs).
+inline bool is_session(int assigner) { return assigner == GW_SESSION || assigner == GW_SESSION_DYNAMIC; }
+
 // Host-time profile of the ingest path (GW_HOST_PROFILE=1: printed by gw_destroy).
 struct HostProf {
     bool on = getenv("GW_HOST_PROFILE") != nullptr;
@@ -2453,7 +2457,7 @@ struct gw_handle {
         int rc;
         if (kg_lo < 0 || kg_hi < kg_lo || kg_hi >= cfg.max_parallelism)
             return fail(GW_E_INVALID, "key-group range [%d, %d] outside [0, %d)", kg_lo, kg_hi, cfg.max_parallelism);
-        if (cfg.assigner == GW_SESSION) return snapshot_sessions_heap(kg_lo, kg_hi, buf, cap, len);
+        if (is_session(cfg.assigner)) return snapshot_sessions_heap(kg_lo, kg_hi, buf, cap, len);
         if (cfg.assigner == GW_COUNT_TUMBLING) return snapshot_count_heap(kg_lo, kg_hi, buf, cap, len);
         KhmHost kh;
         std::vector<int64_t> ent;
@@ -2490,7 +2494,7 @@ struct gw_handle {
         const int64_t ew0 = session_entry_words(sess), ew = ew0 + snap::hash_bytes(hd) / 4;  // fixed entries: words
         bool same = hd.version == slot_blob_version() && hd.agg == cfg.agg && hd.assigner == cfg.assigner &&
                     hd.max_parallelism == cfg.max_parallelism;
-        if (cfg.assigner == GW_SESSION) same = same && hd.gap == cfg.gap && !(hd.flags & ~snap::kKeyHashes);
+        if (is_session(cfg.assigner)) same = same && hd.gap == cfg.gap && !(hd.flags & ~snap::kKeyHashes);
         else if (cfg.assigner == GW_COUNT_TUMBLING) same = same && hd.size == cfg.size && !(hd.flags & ~snap::kKeyHashes);
         else same = same && hd.gap == cfg.gap && hd.size == cfg.size && hd.slide == cfg.slide && hd.reserved == (int32_t)ew;
         if (!same) return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
@@ -2498,7 +2502,7 @@ struct gw_handle {
         std::vector<int64_t> ent, hkeys;
         std::vector<int32_t> hvals;
         int rc = GW_OK;
-        if (cfg.assigner == GW_SESSION) {
+        if (is_session(cfg.assigner)) {
             rc = parse_session_heap(hd, c, ent, hkeys, hvals);
         } else if (cfg.assigner == GW_COUNT_TUMBLING) {
             rc = parse_count_heap(hd, c, ent, hkeys, hvals);
@@ -2718,6 +2722,8 @@ static int validate(const gw_config* c, std::string& why) {
             why = "EventTimeSessionWindows parameters must satisfy 0 < size";
             return GW_E_INVALID;
         }
+    } else if (c->assigner == GW_SESSION_DYNAMIC) {
+        // nothing to check here: every record brings its gap (gw_ingest_gap*)
     } else if (c->assigner == GW_COUNT_TUMBLING || c->assigner == GW_COUNT_SLIDING) {
         const int64_t slide = c->assigner == GW_COUNT_SLIDING ? c->slide : c->size;
         if (c->size <= 0 || slide <= 0) {
@@ -2860,6 +2866,7 @@ int gw_create(const gw_config* cfg, gw_handle** out) {
     gw_handle* h = new (std::nothrow) gw_handle();
     if (!h) { g_create_error = "out of host memory"; return GW_E_OOM; }
     h->cfg = *cfg;
+    if (cfg->assigner == GW_SESSION_DYNAMIC) h->cfg.gap = h->cfg.size = h->cfg.slide = 0;  // ignored (blob headers carry 0)
     if (const char* u = getenv("GW_INGEST_UNROLL")) h->ingest_unroll = atoi(u);
     if (const char* u = getenv("GW_REGION_MIN_BATCH")) h->region_min_batch = atoll(u);
     if (const char* u = getenv("GW_BUFFER_RECORDS")) h->buf_limit = std::max<int64_t>(atoll(u), 1);
@@ -2903,11 +2910,11 @@ int gw_create(const gw_config* cfg, gw_handle** out) {
 
     if ((cfg->flags & GW_FLAG_BY_LAST) && !(cfg->flags & GW_FLAG_BY_FIELD))
         return bail(GW_E_INVALID, "GW_FLAG_BY_LAST without GW_FLAG_BY_FIELD");
-    if (cfg->assigner == GW_SESSION || cfg->assigner == GW_COUNT_TUMBLING || cfg->assigner == GW_COUNT_SLIDING) {
+    if (is_session(cfg->assigner) || cfg->assigner == GW_COUNT_TUMBLING || cfg->assigner == GW_COUNT_SLIDING) {
         if (cfg->flags & (GW_FLAG_FIRST_ELEMENT | GW_FLAG_BY_FIELD))
             return bail(GW_E_UNSUPPORTED, "first-element rows are for tumbling and sliding event-time windows");
         h->session = true;  // the per-key slot path (session merging or count windows)
-        rc = session_create(h->sess, *cfg, cap, h->stream, h->d_st, why);
+        rc = session_create(h->sess, h->cfg, cap, h->stream, h->d_st, why);
         if (rc) return bail(rc, why);
         hipStreamSynchronize(h->stream);
         *out = h;
@@ -3041,18 +3048,21 @@ int gw_destroy(gw_handle* h) {
     return GW_OK;
 }
 
+// gap: the gap column of a GW_SESSION_DYNAMIC handle (gw_ingest_gap*), nullptr otherwise.
 static int ingest_device_impl(gw_handle* h, int64_t n, const int64_t* key, const int64_t* ts,
-                              const int64_t* val) {
+                              const int64_t* val, const int64_t* gap = nullptr) {
     if (h->session) {
         // the grouping sort takes < 2^30 records (gw_sort.h kSortMaxRecords): larger calls go
         // in pieces, each at the same watermark -- the reference processes them one by one
         // anyway, and every piece keeps its records' arrival order
         for (int64_t off = 0; off < n || (n <= 0 && off == 0); off += kSortMaxRecords) {
             const int64_t c = std::min<int64_t>(kSortMaxRecords, n - off);
-            int rc = session_ingest(h->sess, c, key + off, ts ? ts + off : nullptr, val ? val + off : nullptr, h->wm,
-                                    h->err);
+            int rc = session_ingest(h->sess, c, key + off, ts ? ts + off : nullptr, val ? val + off : nullptr,
+                                    gap ? gap + off : nullptr, h->wm, h->err);
             if (rc != GW_OK) {
-                if (rc == GW_E_DEVICE || rc == GW_E_NO_TIMESTAMP || rc == GW_E_RANGE) h->failed = true;
+                // (GW_E_INVALID of a piece: a record's gap is not positive)
+                if (rc == GW_E_DEVICE || rc == GW_E_NO_TIMESTAMP || rc == GW_E_RANGE || (gap && rc == GW_E_INVALID))
+                    h->failed = true;
                 return rc;
             }
             if (n <= 0) break;
@@ -3380,6 +3390,13 @@ int gw_drain_payload(gw_handle* h, int64_t* key, int64_t* start, int64_t* end, v
 
 static int stage_ingest(gw_handle* h, int slot, int64_t n, bool with_hash, bool with_value);
 
+static const char* const kNeedsGap =
+    "GW_SESSION_DYNAMIC handle: records need their gap column (gw_ingest_gap / gw_ingest_gap_device)";
+static int ingest_device_cols(gw_handle* h, int64_t n, const int64_t* d_key, const int32_t* d_key_hash,
+                              const int64_t* d_ts, const void* d_value, const int64_t* d_gap, void* stream);
+static const char* const kDynUnsupported =
+    "%s is not supported on a GW_SESSION_DYNAMIC handle (ingest columns with gw_ingest_gap*)";
+
 int gw_ingest(gw_handle* h, int64_t n, const int64_t* key, const int32_t* key_hash, const int64_t* ts,
               const void* value) {
     if (!h) return GW_E_INVALID;
@@ -3389,6 +3406,7 @@ int gw_ingest(gw_handle* h, int64_t n, const int64_t* key, const int32_t* key_ha
         return GW_OK;
     }
     if (h->failed) return h->fail(GW_E_STATE, "operator failed earlier: %s", h->err.c_str());
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC) return h->fail(GW_E_INVALID, "%s", kNeedsGap);
     if (n < 0 || (n > 0 && (!key || !ts))) return h->fail(GW_E_INVALID, "null key/ts column");
     if (n > 0 && !value && h->cfg.agg != GW_COUNT) return h->fail(GW_E_INVALID, "value column required");
     if (h->slots_out && n > 0)  // gw_ingest copies through the same pinned slots the caller now fills
@@ -3489,6 +3507,7 @@ static int stage_ingest(gw_handle* h, int slot, int64_t n, bool with_hash, bool 
 int gw_stage_alloc(gw_handle* h, int32_t slots, int64_t cap) {
     if (!h || slots < 1 || slots > 4096 || cap < 1) return GW_E_INVALID;
     if (!h->kids.empty() || h->fe) return h->fail(GW_E_UNSUPPORTED, "staged ingest on a composite / first-element handle");
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC) return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "staged ingest");
     hipSetDevice(h->cfg.device);
     return h->ensure_stage(cap, slots);
 }
@@ -3535,6 +3554,58 @@ int gw_ingest_device(gw_handle* h, int64_t n, const int64_t* d_key, const int32_
         FOR_KIDS(gw_ingest_device(kid, n, d_key, d_key_hash, d_ts, d_value, stream));
         return GW_OK;
     }
+    if (h->failed) return h->fail(GW_E_STATE, "operator failed earlier: %s", h->err.c_str());
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC) return h->fail(GW_E_INVALID, "%s", kNeedsGap);
+    return ingest_device_cols(h, n, d_key, d_key_hash, d_ts, d_value, nullptr, stream);
+}
+
+int gw_ingest_gap_device(gw_handle* h, int64_t n, const int64_t* d_key, const int32_t* d_key_hash, const int64_t* d_ts,
+                         const void* d_value, const int64_t* d_gap, void* stream) {
+    if (!h) return GW_E_INVALID;
+    if (h->cfg.assigner != GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_INVALID, "gw_ingest_gap*: not a GW_SESSION_DYNAMIC handle");
+    if (n > 0 && !d_gap) return h->fail(GW_E_INVALID, "null gap column");
+    return ingest_device_cols(h, n, d_key, d_key_hash, d_ts, d_value, d_gap, stream);
+}
+
+// Host columns of a dynamic-gap handle: one device copy of each on the handle's stream
+// (a bounce buffer of the call's own), then the device path.
+int gw_ingest_gap(gw_handle* h, int64_t n, const int64_t* key, const int32_t* key_hash, const int64_t* ts,
+                  const void* value, const int64_t* gap) {
+    if (!h) return GW_E_INVALID;
+    if (h->cfg.assigner != GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_INVALID, "gw_ingest_gap*: not a GW_SESSION_DYNAMIC handle");
+    if (h->failed) return h->fail(GW_E_STATE, "operator failed earlier: %s", h->err.c_str());
+    if (n < 0 || (n > 0 && (!key || !ts))) return h->fail(GW_E_INVALID, "null key/ts column");
+    if (n > 0 && !gap) return h->fail(GW_E_INVALID, "null gap column");
+    if (n > 0 && !value && h->cfg.agg != GW_COUNT) return h->fail(GW_E_INVALID, "value column required");
+    if (n == 0) return GW_OK;
+    hipSetDevice(h->cfg.device);
+    const int ncol = value ? 4 : 3;
+    int64_t* d = nullptr;
+    int32_t* dh = nullptr;
+    if (hipMalloc((void**)&d, (size_t)n * 8 * ncol) != hipSuccess) return h->fail(GW_E_OOM, "gap ingest staging");
+    if (key_hash && hipMalloc((void**)&dh, (size_t)n * 4) != hipSuccess) {
+        hipFree(d);
+        return h->fail(GW_E_OOM, "gap ingest staging");
+    }
+    hipError_t e = hipMemcpyAsync(d, key, n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + n, ts, n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * n, gap, n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && value) e = hipMemcpyAsync(d + 3 * n, value, n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && dh) e = hipMemcpyAsync(dh, key_hash, n * 4, hipMemcpyHostToDevice, h->stream);
+    const int rc = e == hipSuccess
+                       ? ingest_device_cols(h, n, d, dh, d + n, value ? d + 3 * n : nullptr, d + 2 * n, h->stream)
+                       : h->fail(GW_E_DEVICE, "H2D: %s", hipGetErrorString(e));
+    hipStreamSynchronize(h->stream);  // the staging is read; a record error surfaces at the next call
+    hipFree(d);
+    if (dh) hipFree(dh);
+    return rc;
+}
+
+// gw_ingest_device / gw_ingest_gap_device on a plain handle (d_gap: the dynamic-gap column).
+static int ingest_device_cols(gw_handle* h, int64_t n, const int64_t* d_key, const int32_t* d_key_hash,
+                              const int64_t* d_ts, const void* d_value, const int64_t* d_gap, void* stream) {
     h->hp.mark();
     if (h->failed) return h->fail(GW_E_STATE, "operator failed earlier: %s", h->err.c_str());
     if (n < 0 || (n > 0 && (!d_key || !d_ts))) return h->fail(GW_E_INVALID, "null key/ts column");
@@ -3553,7 +3624,7 @@ int gw_ingest_device(gw_handle* h, int64_t n, const int64_t* d_key, const int32_
     if (n == 0) return GW_OK;
     h->hp.lap(5);
     int rc = h->check_keys(h->pk_w ? h->pk_from : n, d_key, d_key_hash);  // (packed words: routed already)
-    if (rc == GW_OK) rc = ingest_device_impl(h, n, d_key, d_ts, (const int64_t*)d_value);
+    if (rc == GW_OK) rc = ingest_device_impl(h, n, d_key, d_ts, (const int64_t*)d_value, d_gap);
     if (foreign) {
         hipEventRecord(h->ev_out, h->stream);
         hipStreamWaitEvent(ps, h->ev_out, 0);
@@ -3565,6 +3636,8 @@ int gw_ingest_packed_device(gw_handle* h, int64_t n_other, const int64_t* d_key,
                             const int64_t* d_value, int64_t n_words, const uint64_t* d_words, const gw_pack_geom* g,
                             void* stream) {
     if (!h) return GW_E_INVALID;
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "gw_ingest_packed_device");
     if (n_other < 0 || n_words < 0 || (n_words > 0 && (!d_words || !g || !g->enabled || g->pane <= 0)))
         return h->fail(GW_E_INVALID, "gw_ingest_packed_device: bad word arguments");
     if (n_words == 0) return gw_ingest_device(h, n_other, d_key, nullptr, d_ts, d_value, stream);
@@ -3803,6 +3876,8 @@ int gw_ingest_serialized_device(gw_handle* h, const void* d_bytes, int64_t nbyte
                                 void* stream, int64_t* consumed, int64_t* rows_fired) {
     if (!h) return GW_E_INVALID;
     if (h->fe) return h->fail(GW_E_UNSUPPORTED, "network-buffer ingest of first-element rows is not supported");
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "network-buffer ingest (gw_ingest_serialized*)");
     if (!h->kids.empty()) {  // each child decodes the channel (same bytes consumed by all)
         int64_t sum = 0;
         for (gw_handle* kid : h->kids) {
@@ -3838,6 +3913,8 @@ int gw_ingest_serialized(gw_handle* h, const void* bytes, int64_t nbytes, const 
                          int64_t* consumed, int64_t* rows_fired) {
     if (!h) return GW_E_INVALID;
     if (h->fe) return h->fail(GW_E_UNSUPPORTED, "network-buffer ingest of first-element rows is not supported");
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "network-buffer ingest (gw_ingest_serialized*)");
     if (!h->kids.empty()) {
         int64_t sum = 0;
         for (gw_handle* kid : h->kids) {
@@ -3915,7 +3992,11 @@ int gw_advance_watermark(gw_handle* h, int64_t wm, int64_t* rows_fired) {
         if (wm > h->wm) {
             rc = session_fire(h->sess, wm, &fired, h->err);
             if (rc == GW_OK) h->wm = wm;
-            else if (rc == GW_E_DEVICE) h->failed = true;
+            // a deferred ingest's record error (no timestamp, window end out of range, a gap
+            // that is not positive) surfaces here and fails the operator as it does at ingest
+            else if (rc == GW_E_DEVICE || rc == GW_E_NO_TIMESTAMP || rc == GW_E_RANGE ||
+                     (rc == GW_E_INVALID && h->cfg.assigner == GW_SESSION_DYNAMIC))
+                h->failed = true;
         }
         h->stats.rows_fired += fired;
         if (rows_fired) *rows_fired = fired;
@@ -4735,7 +4816,7 @@ int gw_enable_kernel_timing(gw_handle* h, int enable) {
     h->timing = enable != 0;
     h->timing_every = enable > 1 ? enable : 1;
     h->timing_ctr = 0;
-    if (h->sess) session_enable_timing(h->sess, h->timing);
+    if (h->sess) session_enable_timing(h->sess, enable);
     return GW_OK;
 }
 

@@ -13,8 +13,9 @@ struct SessionState;
 int session_create(SessionState*& s, const gw_config& cfg, int64_t cap, hipStream_t stream, DevStatus* unused,
                    std::string& why);
 void session_destroy(SessionState* s);
+// gap: the per-record gap column of a GW_SESSION_DYNAMIC handle (nullptr otherwise).
 int session_ingest(SessionState* s, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* val,
-                   int64_t wm, std::string& err);
+                   const int64_t* gap, int64_t wm, std::string& err);
 int session_fire(SessionState* s, int64_t wm, int64_t* fired, std::string& err);
 void session_rows(SessionState* s, int64_t** k, int64_t** st, int64_t** en, int64_t** r, int64_t* total);
 int session_refresh(SessionState* s, std::string& err);
@@ -34,7 +35,8 @@ int session_pending_late(SessionState* s, int64_t* n, std::string& err);
 int session_drain_late(SessionState* s, int64_t* key, int64_t* ts, int64_t* val, int64_t cap, int64_t* n,
                        std::string& err);
 void session_stats(SessionState* s, gw_stats* out);
-void session_enable_timing(SessionState* s, bool on);
+// level: 0 off, 1 ingest and fire, 2 also the session ingest's prep, sort and segment (which 6-8).
+void session_enable_timing(SessionState* s, int level);
 int session_kernel_time(SessionState* s, int which, double* ms, int64_t* launches);
 
 }  // namespace gw

@@ -51,7 +51,8 @@ struct SegArgs {
     const int64_t* ts;
     const int64_t* val;
     const int64_t* rec;     // (ts, value) per record in arrival order, 16-B aligned: one gather per record
-    int64_t gap;
+                            // (DYN: (ts, value, gap, 0), 32-B aligned: still one 64-B sector per record)
+    int64_t gap;            // the constant gap (DYN: unused, every record carries its own)
     int64_t wm;             // current watermark (all records of the batch see it)
     int64_t lateness;       // allowed lateness (WindowOperator.allowedLateness)
     int purge;              // PurgingTrigger: a fired session keeps an empty state until cleanup
@@ -75,6 +76,7 @@ struct SegArgs {
                             // st->spills: replayed after a regrow
     int64_t* pu_ts;
     int64_t* pu_val;
+    int64_t* pu_gap;        // DYN: their gaps
 };
 
 struct Sess {
@@ -227,7 +229,8 @@ __device__ __forceinline__ void sl_put(const SessList& l, int q, const Sess& v) 
 }
 
 // MergingWindowSet.addWindow + WindowOperator.processElement (merging branch) for one
-// element: the window [ts, ts + gap) merges with every session it intersects (inclusive);
+// element: the window [ts, ts + gap) (gap: the assigner's constant, or the element's own,
+// DynamicEventTimeSessionWindows.assignWindows) merges with every session it intersects (inclusive);
 // a window that merges with nothing and is already late is skipped (late: counted or sent
 // to the side output); a merged or new window whose max timestamp <= watermark fires at
 // once (EventTimeTrigger.onElement FIRE; PurgingTrigger purges), otherwise its timer is
@@ -235,11 +238,11 @@ __device__ __forceinline__ void sl_put(const SessList& l, int q, const Sess& v) 
 // side output are written (a trial replay that may be abandoned).
 template <int AGG>
 __device__ __forceinline__ bool add_element_tv(const SegArgs& a, const SessList& l, int& cnt, int cap, int64_t key,
-                                               int64_t ts, int64_t value, unsigned long long& late,
+                                               int64_t ts, int64_t value, int64_t gap, unsigned long long& late,
                                                unsigned long long& merges, unsigned long long& flags, bool dry) {
     struct { int64_t ts, v; } tv{ts, value};
     int64_t we;
-    if (__builtin_add_overflow(ts, a.gap, &we)) { flags |= GW_DF_RANGE; return true; }
+    if (__builtin_add_overflow(ts, gap, &we)) { flags |= GW_DF_RANGE; return true; }
     const int64_t ws = ts;
     int lo = -1, hi = -1;
     for (int q = 0; q < cnt; ++q) {
@@ -300,14 +303,23 @@ __device__ __forceinline__ bool add_element_tv(const SegArgs& a, const SessList&
     return true;
 }
 
-// The same for element `idx` of the batch, read from the (ts, value) pairs of k_sess_prep.
-template <int AGG>
+// The same for element `idx` of the batch, read from the (ts, value) pairs of k_sess_prep
+// (DYN: its (ts, value, gap, 0) records: the pair and the gap from one 32-B aligned record).
+// A record whose gap is not positive has failed the operator in the prep (GW_DF_BAD_GAP): it
+// is skipped.
+struct alignas(16) TsVal { int64_t ts, v; };
+template <int AGG, bool DYN>
 __device__ __forceinline__ bool add_element(const SegArgs& a, const SessList& l, int& cnt, int cap, int64_t key,
                                             int64_t idx, unsigned long long& late, unsigned long long& merges,
                                             unsigned long long& flags, bool dry = false) {
-    struct alignas(16) TsVal { int64_t ts, v; };
-    const TsVal tv = (GW_SEG_EXP & 1) ? TsVal{a.wm + 1 + (int64_t)(idx & 7), 1} : reinterpret_cast<const TsVal*>(a.rec)[idx];
-    return add_element_tv<AGG>(a, l, cnt, cap, key, tv.ts, tv.v, late, merges, flags, dry);
+    const int64_t at = DYN ? 2 * idx : idx;
+    const TsVal tv = (GW_SEG_EXP & 1) ? TsVal{a.wm + 1 + (int64_t)(idx & 7), 1} : reinterpret_cast<const TsVal*>(a.rec)[at];
+    int64_t gap = a.gap;
+    if (DYN) {
+        gap = (GW_SEG_EXP & 1) ? 1 : a.rec[4 * idx + 2];
+        if (gap <= 0) return true;
+    }
+    return add_element_tv<AGG>(a, l, cnt, cap, key, tv.ts, tv.v, gap, late, merges, flags, dry);
 }
 
 // Main pass: one thread per key's run.  The run's elements replay against the key's
@@ -318,7 +330,7 @@ __device__ __forceinline__ bool add_element(const SegArgs& a, const SessList& l,
 // the dry replay is the real one.
 // One key's records among the group [i, j) (those whose slot is `slot`, L of them, the first
 // at i), in arrival order.
-template <int AGG>
+template <int AGG, bool DYN>
 __device__ __forceinline__ void seg_slot(const SegArgs& a, const SessList& l, int64_t i, int64_t j, uint32_t slot,
                                          int64_t L, unsigned long long& late, unsigned long long& merges,
                                          unsigned long long& flags) {
@@ -340,7 +352,7 @@ __device__ __forceinline__ void seg_slot(const SegArgs& a, const SessList& l, in
         // whole-slot groups (gshift 0): every record of [i, j) is the slot's, no slot re-read
         for (int64_t r = i; r < j && ok; ++r)
             if (a.gshift == 0 || a.slot[r] == slot)
-                ok = add_element<AGG>(a, l, cnt, kLaneSess, key, a.perm[r], late, merges, flags, dry);
+                ok = add_element<AGG, DYN>(a, l, cnt, kLaneSess, key, a.perm[r], late, merges, flags, dry);
         if (!ok || !dry || !effects) break;
         dry = false;
         late = l0;
@@ -403,7 +415,7 @@ __device__ __forceinline__ bool seg_is_item(const SegArgs& a, int64_t i) {
     return true;
 }
 
-template <int AGG>
+template <int AGG, bool DYN>
 __device__ __forceinline__ void seg_run(const SegArgs& a, const SessList& l, int64_t i, unsigned long long& late,
                                         unsigned long long& merges, unsigned long long& flags) {
     const uint32_t slot = a.slot[i], grp = slot >> a.gshift;
@@ -415,26 +427,26 @@ __device__ __forceinline__ void seg_run(const SegArgs& a, const SessList& l, int
     }
     if ((int64_t)slot == a.t.cap + 1) {  // keys k_sess_prep found no slot for: replayed after a regrow
         unsigned long long at = atomicAdd(&a.st->spills, (unsigned long long)L);
-        struct alignas(16) TsVal { int64_t ts, v; };
         for (int64_t r = i; r < j; ++r) {
             if (a.slot[r] != slot) continue;
             const uint32_t idx = a.perm[r];
-            const TsVal tv = reinterpret_cast<const TsVal*>(a.rec)[idx];
+            const TsVal tv = reinterpret_cast<const TsVal*>(a.rec)[DYN ? 2 * (int64_t)idx : (int64_t)idx];
             a.pu_key[at] = a.key[idx];
             a.pu_ts[at] = tv.ts;
             a.pu_val[at] = tv.v;
+            if (DYN) a.pu_gap[at] = a.rec[4 * (int64_t)idx + 2];
             ++at;
         }
         return;
     }
-    seg_slot<AGG>(a, l, i, j, slot, L, late, merges, flags);
+    seg_slot<AGG, DYN>(a, l, i, j, slot, L, late, merges, flags);
 }
 
 // Each wave takes kSegChunk consecutive records, compacts their work items into LDS with
 // ballots, and replays them 64 at a time: every lane owns a run (about one record in
 // three starts one), not one lane per record.
 constexpr int kSegChunk = 512;
-template <int AGG>
+template <int AGG, bool DYN>
 __global__ void __launch_bounds__(kSegThreads) k_sess_segment(SegArgs a) {
     __shared__ int64_t lane[5 * kLaneSess * kSegThreads];
     __shared__ uint32_t heads[kSegThreads / 64][kSegChunk];
@@ -451,7 +463,7 @@ __global__ void __launch_bounds__(kSegThreads) k_sess_segment(SegArgs a) {
         nh += __popcll(b);
     }
     __syncthreads();
-    for (int q = ln; q < nh; q += 64) seg_run<AGG>(a, l, base + heads[w][q], late, merges, flags);
+    for (int q = ln; q < nh; q += 64) seg_run<AGG, DYN>(a, l, base + heads[w][q], late, merges, flags);
     late = wave_sum(late);
     merges = wave_sum(merges);
     flags = wave_ior(flags);
@@ -502,7 +514,7 @@ __global__ void __launch_bounds__(256) k_sess_migrate(TableView t, TableView w, 
 // Wide pass: one thread per punted run, against the key's wide slot in global memory.  A
 // key not yet wide moves there first.  A run that could exceed K2 sessions is left for a
 // retry after the host widens the table (nothing is written or emitted for it).
-template <int AGG>
+template <int AGG, bool DYN>
 __global__ void __launch_bounds__(256) k_sess_wide(SegArgs a) {
     unsigned long long late = 0, merges = 0, flags = 0, ins = 0;
     for (int64_t r0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r0 < a.n_runs;
@@ -550,7 +562,7 @@ __global__ void __launch_bounds__(256) k_sess_wide(SegArgs a) {
         }
         const SessList l{d + 2, 1, kWideWords};
         for (int64_t r = i; r < j; ++r)
-            if (a.slot[r] == slot) add_element<AGG>(a, l, cnt, a.w.ring, key, a.perm[r], late, merges, flags);
+            if (a.slot[r] == slot) add_element<AGG, DYN>(a, l, cnt, a.w.ring, key, a.perm[r], late, merges, flags);
         d[1] = cnt;
         due_of(a.w)[g2] = wide_due(d, a.lateness);
     }
@@ -561,9 +573,13 @@ __global__ void __launch_bounds__(256) k_sess_wide(SegArgs a) {
     if (ins) atomicAdd(&a.st->pad[2], ins);
 }
 
-__global__ void __launch_bounds__(256) k_sess_prep(const int64_t* key, const int64_t* ts, const int64_t* val, int64_t n,
-                                                   TableView t, uint32_t* slot, int64_t* rec,
-                                                   DevStatus* st) {
+// DYN: the record also carries its gap (32-B records); a gap that is not positive fails the
+// operator (DynamicEventTimeSessionWindows.assignWindows: "Dynamic session time gap must
+// satisfy 0 < gap").
+template <bool DYN>
+__global__ void __launch_bounds__(256) k_sess_prep(const int64_t* key, const int64_t* ts, const int64_t* val,
+                                                   const int64_t* gap, int64_t n, TableView t, uint32_t* slot,
+                                                   int64_t* rec, DevStatus* st) {
     unsigned long long ins = 0, flags = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {  // the main pass's counters (nothing reads them before it)
         st->overflow = 0;
@@ -577,7 +593,15 @@ __global__ void __launch_bounds__(256) k_sess_prep(const int64_t* key, const int
         ins += inserted;
         if (s < 0) { flags |= GW_DF_TABLE_FULL; s = t.cap + 1; }  // no slot: sorts last, the segment punts it
         slot[i] = (uint32_t)s;  // (the arrival index, perm, is made by the sort's first pass)
-        if (rec) {
+        if (DYN) {
+            const int64_t g = gap[i];
+            if (g <= 0) flags |= GW_DF_BAD_GAP;
+            int64_t* r = rec + 4 * i;
+            r[0] = ts[i];
+            r[1] = val ? val[i] : 0;
+            r[2] = g;
+            r[3] = 0;
+        } else if (rec) {
             rec[2 * i] = ts[i];
             rec[2 * i + 1] = val ? val[i] : 0;
         }
@@ -1126,6 +1150,7 @@ __global__ void __launch_bounds__(256) k_cnt_restore(TableView t, const int64_t*
 }
 
 // --------------------------------------------------------------------------- host
+constexpr int kTimers = 5;
 struct SessionState {
     gw_config cfg{};
     hipStream_t stream = nullptr;
@@ -1140,6 +1165,8 @@ struct SessionState {
     int64_t* mig = nullptr;  // migration lists (main pass -> wide table)
     int64_t* rec = nullptr;  // sessions: (ts, value) per record in arrival order
     int64_t* pu_rec = nullptr;  // sessions: records of keys the prep found no slot for, key | ts | value
+                                // (| gap with per-element gaps)
+    bool dyn = false;        // GW_SESSION_DYNAMIC: every record carries its gap (the DYN kernels)
     bool fresh = false;      // h_st matches the device (nothing launched since the last refresh)
     // An ingest whose host follow-up (sort_tail: migrations, the wide pass, records without a
     // slot) waits for the next sync: the fire launched right after it checks the device
@@ -1168,11 +1195,13 @@ struct SessionState {
     int64_t wm = INT64_MIN;
     gw_stats stats{};
     bool timing = false;
+    bool timing_split = false;  // also the ingest's prep, sort and segment, each by itself
     bool count_mode = false;  // GW_COUNT_TUMBLING / GW_COUNT_SLIDING (same slot table and row plumbing)
     CountGeom cg{};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending[2], ev_pool;
-    double t_total[2] = {0, 0};
-    int64_t t_count[2] = {0, 0};
+    // timers: 0 ingest, 1 fire, 2-4 the session ingest's prep, sort and segment
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending[kTimers], ev_pool;
+    double t_total[kTimers] = {};
+    int64_t t_count[kTimers] = {};
 };
 
 static int dev_err(std::string& err, const char* what, hipError_t e) {
@@ -1188,7 +1217,7 @@ static int dev_err(std::string& err, const char* what, hipError_t e) {
     } while (0)
 
 static void resolve_timers(SessionState* s) {
-    for (int w = 0; w < 2; ++w) {
+    for (int w = 0; w < kTimers; ++w) {
         for (auto& p : s->ev_pending[w]) {
             float ms = 0;
             if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) { s->t_total[w] += ms; s->t_count[w]++; }
@@ -1205,6 +1234,20 @@ static std::pair<hipEvent_t, hipEvent_t> get_ev(SessionState* s) {
     return p;
 }
 
+// One timed stretch inside the ingest (kernel timing level 2: the event records between the
+// kernels cost ~2% of a 10M-record step, so plain timing leaves them out): lap_begin ... lap_end(w).
+typedef std::pair<hipEvent_t, hipEvent_t> EvPair;
+static void lap_begin(SessionState* s, EvPair& ev) {
+    if (!s->timing_split) return;
+    ev = get_ev(s);
+    hipEventRecord(ev.first, s->stream);
+}
+static void lap_end(SessionState* s, int w, const EvPair& ev) {
+    if (!s->timing_split) return;
+    hipEventRecord(ev.second, s->stream);
+    s->ev_pending[w].push_back(ev);
+}
+
 static int sb_finish(SessionState* s, std::string& err);
 
 // Device counters -> host view (one host sync), then a pending ingest's follow-up.
@@ -1218,6 +1261,10 @@ static int sess_sync(SessionState* s, std::string& err) {
         err = "Record has Long.MIN_VALUE timestamp (= no timestamp marker). Did you forget to call "
               "'DataStream.assignTimestampsAndWatermarks(...)'?";
         return GW_E_NO_TIMESTAMP;
+    }
+    if (s->h_st->flags & GW_DF_BAD_GAP) {  // DynamicEventTimeSessionWindows.assignWindows
+        err = "Dynamic session time gap must satisfy 0 < gap";
+        return GW_E_INVALID;
     }
     if (s->h_st->flags & GW_DF_RANGE) {
         err = "session window end overflows int64";
@@ -1275,6 +1322,7 @@ int session_create(SessionState*& out, const gw_config& cfg, int64_t cap, hipStr
                    std::string& why) {
     SessionState* s = new SessionState();
     s->cfg = cfg;
+    s->dyn = cfg.assigner == GW_SESSION_DYNAMIC;
     s->stream = stream;
     s->tv.agg = cfg.agg;
     s->wv.agg = cfg.agg;
@@ -1317,7 +1365,7 @@ void session_destroy(SessionState* s) {
     hipFree(s->sort_tmp);
     hipFree(s->o_key); hipFree(s->o_start); hipFree(s->o_end); hipFree(s->o_res);
     for (auto* p : s->lo_buf) hipFree(p);
-    for (int w = 0; w < 2; ++w) for (auto& p : s->ev_pending[w]) s->ev_pool.push_back(p);
+    for (int w = 0; w < kTimers; ++w) for (auto& p : s->ev_pending[w]) s->ev_pool.push_back(p);
     for (auto& p : s->ev_pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     delete s;
 }
@@ -1338,8 +1386,8 @@ static int ensure_bufs(SessionState* s, int64_t n, std::string& err) {
     SCHECK(hipMalloc((void**)&s->r0, c * 4));
     SCHECK(hipMalloc((void**)&s->r1, c * 4));
     if (!s->count_mode) SCHECK(hipMalloc((void**)&s->mig, (size_t)c * (2 + kWideWords * kLaneSess) * 8));
-    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->rec, (size_t)c * 16));
-    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->pu_rec, (size_t)c * 24));
+    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->rec, (size_t)c * (s->dyn ? 32 : 16)));
+    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->pu_rec, (size_t)c * (s->dyn ? 32 : 24)));
     const size_t bytes = (size_t)sort_scratch_bytes(c);
     SCHECK(hipMalloc(&s->sort_tmp, bytes));
     s->sort_tmp_bytes = bytes;
@@ -1362,8 +1410,11 @@ static int sort_by_slot(SessionState* s, int64_t n, int64_t cap, const uint32_t*
     if (const char* e = getenv("GW_SESSION_SORT_BITS")) sort_bits = std::max(1, atoi(e));
     s->gshift = s->count_mode ? 0 : std::min(4, std::max(0, bits - sort_bits));
     int alt = 0;
+    EvPair ev;
+    lap_begin(s, ev);
     SCHECK(sort_pairs_u32(s->slot[0], s->perm[0], s->slot[1], s->perm[1], n, s->gshift, bits, s->sort_tmp, s->stream,
                           &alt, /*iota=*/true));
+    lap_end(s, 3, ev);
     *sk = s->slot[alt];
     *sp = s->perm[alt];
     return GW_OK;
@@ -1466,7 +1517,8 @@ int session_drain_late(SessionState* s, int64_t* key, int64_t* ts, int64_t* val,
 // Slot per record and the stable grouping by slot (both modes).  Grows the main table to
 // keep its load below 0.7 for `n` possible new keys.
 static int group_records(SessionState* s, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* val,
-                         const uint32_t** sk, const uint32_t** sp, std::string& err, bool defer = false) {
+                         const int64_t* gap, const uint32_t** sk, const uint32_t** sp, std::string& err,
+                         bool defer = false) {
     int rc;
     if ((double)(s->h_st->used_slots + n) > 0.7 * (double)s->tv.cap &&
         ((double)s->h_st->used_slots > 0.7 * (double)s->tv.cap ||
@@ -1477,8 +1529,15 @@ static int group_records(SessionState* s, int64_t n, const int64_t* key, const i
     }
     if ((rc = ensure_bufs(s, n, err))) return rc;
     for (int attempt = 0;; ++attempt) {
-        hipLaunchKernelGGL(k_sess_prep, dim3(grid_of(n)), dim3(256), 0, s->stream, key, ts, val, n, s->tv, s->slot[0],
-                           s->count_mode ? nullptr : s->rec, s->d_st);
+        EvPair ev;
+        lap_begin(s, ev);
+        if (s->dyn)
+            hipLaunchKernelGGL(k_sess_prep<true>, dim3(grid_of(n)), dim3(256), 0, s->stream, key, ts, val, gap, n, s->tv,
+                               s->slot[0], s->rec, s->d_st);
+        else
+            hipLaunchKernelGGL(k_sess_prep<false>, dim3(grid_of(n)), dim3(256), 0, s->stream, key, ts, val, nullptr, n,
+                               s->tv, s->slot[0], s->count_mode ? nullptr : s->rec, s->d_st);
+        lap_end(s, 2, ev);
         // deferred (sessions): no host wait here; records without a slot sort last and the
         // segment punts them for a replay after a regrow (sort_tail)
         if (defer && !s->count_mode) break;
@@ -1561,7 +1620,7 @@ static int count_ingest(SessionState* s, int64_t n, const int64_t* key, const in
     if (s->timing) SCHECK(hipEventRecord(ev.first, s->stream));
     const uint32_t* ks;
     const uint32_t* perm;
-    if ((rc = group_records(s, n, key, nullptr, nullptr, &ks, &perm, err))) return rc;
+    if ((rc = group_records(s, n, key, nullptr, nullptr, nullptr, &ks, &perm, err))) return rc;
     if ((rc = launch_count_apply(s, ks, perm, n, val, err))) return rc;
     if (s->timing) {
         SCHECK(hipEventRecord(ev.second, s->stream));
@@ -1629,12 +1688,12 @@ static int sort_tail(SessionState* s, SegArgs a, int64_t wm, std::string& err);
 // runs, records without a slot -- runs at the next sync (sb_finish), and the watermark's fire
 // launched before it skips itself on the device while that work is pending.
 static int ingest_sorted(SessionState* s, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* val,
-                         int64_t wm, std::string& err, bool defer = false) {
+                         const int64_t* gap, int64_t wm, std::string& err, bool defer = false) {
     int rc;
     SegArgs a{};
     static const bool always = getenv("GW_SESSION_SYNC") && atoi(getenv("GW_SESSION_SYNC")) != 0;
     defer = defer && !always && s->cfg.allowed_lateness == 0 && !(s->cfg.flags & GW_FLAG_LATE_SIDE_OUTPUT);
-    if ((rc = group_records(s, n, key, ts, val, &a.slot, &a.perm, err, defer))) return rc;
+    if ((rc = group_records(s, n, key, ts, val, gap, &a.slot, &a.perm, err, defer))) return rc;
     a.rec = s->rec;
     a.gshift = s->gshift;
     a.key = key;
@@ -1648,11 +1707,17 @@ static int ingest_sorted(SessionState* s, int64_t n, const int64_t* key, const i
     a.pu_key = s->pu_rec;
     a.pu_ts = s->pu_rec + C;
     a.pu_val = s->pu_rec + 2 * C;
+    a.pu_gap = s->dyn ? s->pu_rec + 3 * C : nullptr;
     const int64_t per_block = (int64_t)kSegChunk * (kSegThreads / 64);
     const unsigned gs = (unsigned)((n + per_block - 1) / per_block);
-#define L(A) hipLaunchKernelGGL(k_sess_segment<A>, dim3(gs), dim3(kSegThreads), 0, s->stream, a)
+    EvPair sev;
+    lap_begin(s, sev);
+#define L(A)                                                                                                 \
+    if (s->dyn) hipLaunchKernelGGL((k_sess_segment<A, true>), dim3(gs), dim3(kSegThreads), 0, s->stream, a); \
+    else hipLaunchKernelGGL((k_sess_segment<A, false>), dim3(gs), dim3(kSegThreads), 0, s->stream, a)
     GW_AGG_SWITCH(s->cfg.agg, L);
 #undef L
+    lap_end(s, 4, sev);
     SCHECK(hipGetLastError());
     if (defer) {
         s->sort_a = a;
@@ -1692,7 +1757,9 @@ static int sort_tail(SessionState* s, SegArgs a, int64_t wm, std::string& err) {
         a.runs = rin;
         a.n_runs = n_punt;
         a.retry = rout;
-#define L(A) hipLaunchKernelGGL(k_sess_wide<A>, dim3(grid_of(n_punt)), dim3(256), 0, s->stream, a)
+#define L(A)                                                                                                     \
+        if (s->dyn) hipLaunchKernelGGL((k_sess_wide<A, true>), dim3(grid_of(n_punt)), dim3(256), 0, s->stream, a); \
+        else hipLaunchKernelGGL((k_sess_wide<A, false>), dim3(grid_of(n_punt)), dim3(256), 0, s->stream, a)
         GW_AGG_SWITCH(s->cfg.agg, L);
 #undef L
         SCHECK(hipGetLastError());
@@ -1711,7 +1778,7 @@ static int sort_tail(SessionState* s, SegArgs a, int64_t wm, std::string& err) {
     }
     if (n_fail > 0) {
         if ((rc = regrow(s, s->tv, s->tv.cap * 2, s->tv.ring, false, err))) return rc;
-        if ((rc = ingest_sorted(s, n_fail, a.pu_key, a.pu_ts, a.pu_val, wm, err, false))) return rc;
+        if ((rc = ingest_sorted(s, n_fail, a.pu_key, a.pu_ts, a.pu_val, a.pu_gap, wm, err, false))) return rc;
     }
     return GW_OK;
 }
@@ -1724,8 +1791,8 @@ static int sb_finish(SessionState* s, std::string& err) {
     return sort_tail(s, s->sort_a, s->sb_wm, err);
 }
 
-int session_ingest(SessionState* s, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* val, int64_t wm,
-                   std::string& err) {
+int session_ingest(SessionState* s, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* val,
+                   const int64_t* gap, int64_t wm, std::string& err) {
     if (s->count_mode) return count_ingest(s, n, key, val, err);
     int rc;
     if ((rc = begin_launch(s, err))) return rc;
@@ -1733,7 +1800,7 @@ int session_ingest(SessionState* s, int64_t n, const int64_t* key, const int64_t
     if (n > kSortMaxRecords) { err = "batch too large for the grouping sort (split by the caller)"; return GW_E_INVALID; }
     auto ev = s->timing ? get_ev(s) : std::pair<hipEvent_t, hipEvent_t>{};
     if (s->timing) SCHECK(hipEventRecord(ev.first, s->stream));
-    if ((rc = ingest_sorted(s, n, key, ts, val, wm, err, true))) return rc;
+    if ((rc = ingest_sorted(s, n, key, ts, val, gap, wm, err, true))) return rc;
     if (s->timing) {
         SCHECK(hipEventRecord(ev.second, s->stream));
         s->ev_pending[0].push_back(ev);
@@ -1955,12 +2022,15 @@ void session_stats(SessionState* s, gw_stats* out) {
     out->session_slow = s->stats.session_slow;
 }
 
-void session_enable_timing(SessionState* s, bool on) { s->timing = on; }
+void session_enable_timing(SessionState* s, int level) {
+    s->timing = level != 0;
+    s->timing_split = level >= 2;
+}
 
 int session_kernel_time(SessionState* s, int which, double* ms, int64_t* launches) {
     hipStreamSynchronize(s->stream);
     resolve_timers(s);
-    const int w = which ? 1 : 0;
+    const int w = which >= 6 && which <= 8 ? which - 4 : which ? 1 : 0;  // 6-8: prep, sort, segment
     if (ms) *ms = s->t_count[w] ? s->t_total[w] / (double)s->t_count[w] : 0.0;
     if (launches) *launches = s->t_count[w];
     s->t_total[w] = 0;

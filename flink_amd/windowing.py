@@ -4,7 +4,7 @@ Names, argument meaning and error behaviour follow Flink's DataStream windowing 
 so a job (or a harness test) reads the same:
 
   * assigners   TumblingEventTimeWindows.of / SlidingEventTimeWindows.of /
-                EventTimeSessionWindows.with_gap
+                EventTimeSessionWindows.with_gap / DynamicEventTimeSessionWindows.with_dynamic_gap
                 (flink-runtime/.../streaming/api/windowing/assigners/*.java,
                  flink-streaming-java/.../EventTimeSessionWindows.java)
   * triggers    EventTimeTrigger.create(), PurgingTrigger.of(...)
@@ -130,6 +130,28 @@ class EventTimeSessionWindows(WindowAssigner):
 
     def config(self):
         return dict(assigner="session", gap=self.gap)
+
+
+class DynamicEventTimeSessionWindows(WindowAssigner):
+    """DynamicEventTimeSessionWindows.withDynamicGap(extractor): the element's window is
+    [timestamp, timestamp + extractor(element)) (flink-streaming-java/.../assigners/
+    DynamicEventTimeSessionWindows.java).  The operator evaluates the extractor per element
+    (process_element) or takes the gaps as a column (process_batch(..., gaps=))."""
+    kind = "session_dynamic"
+
+    def __init__(self, extractor: Callable[[Any], int]):
+        if extractor is None:
+            raise ValueError("a session gap extractor is required")
+        self.extractor = extractor
+
+    @staticmethod
+    def with_dynamic_gap(extractor: Callable[[Any], int]) -> "DynamicEventTimeSessionWindows":
+        return DynamicEventTimeSessionWindows(extractor)
+
+    withDynamicGap = with_dynamic_gap
+
+    def config(self):
+        return dict(assigner="session_dynamic")
 
 
 class CountWindows(WindowAssigner):
@@ -358,6 +380,9 @@ class GpuWindowOperator:
         self._by = bool(flags & N.FLAG_BY_FIELD)
         self._elems: list = []
         self._buf_p: List[int] = []
+        # per-element session gaps (DynamicEventTimeSessionWindows): the extractor's value per record
+        self._dynamic = a["assigner"] == "session_dynamic"
+        self._buf_g: List[int] = []
         self.output: list = []
         # reduce / aggregate(..., ProcessWindowFunction): window_function(key, (start, end), [result],
         # out) per fired window, out a list the emitted values go to (InternalSingleValueProcess-
@@ -453,6 +478,8 @@ class GpuWindowOperator:
         self._buf_k.append(self._encode_key(self.key_selector(v)))
         self._buf_t.append(int(record.timestamp))
         self._buf_v.append(self.value_selector(v) if self.aggregate != "count" else 0)
+        if self._dynamic:
+            self._buf_g.append(int(self.assigner.extractor(v)))
         if self._payload:
             self._buf_p.append(len(self._elems))
             self._elems.append(v)
@@ -472,6 +499,10 @@ class GpuWindowOperator:
             p = np.asarray(self._buf_p, dtype=np.int64)
             self._buf_p = []
             self.process_batch_payload(k, t, v, p, key_hashes=h)
+        elif self._dynamic:
+            g = np.asarray(self._buf_g, dtype=np.int64)
+            self._buf_g = []
+            self.process_batch(k, t, v, key_hashes=h, gaps=g)
         else:
             self.process_batch(k, t, v, key_hashes=h)
 
@@ -510,8 +541,16 @@ class GpuWindowOperator:
         return out
 
     # columnar surface ------------------------------------------------------------
+    def _check_gaps(self, gaps):
+        if self._dynamic and gaps is None:
+            raise ValueError("a DynamicEventTimeSessionWindows operator needs the gap column (gaps=)")
+        if not self._dynamic and gaps is not None:
+            raise ValueError("gaps= is for DynamicEventTimeSessionWindows operators")
+
     def process_batch(self, keys: np.ndarray, timestamps: np.ndarray, values: Optional[np.ndarray] = None,
-                      key_hashes: Optional[np.ndarray] = None):
+                      key_hashes: Optional[np.ndarray] = None, gaps: Optional[np.ndarray] = None):
+        """gaps: the per-element session gaps in ms (DynamicEventTimeSessionWindows operators)."""
+        self._check_gaps(gaps)
         self._ensure_handle()
         keys = np.ascontiguousarray(keys, dtype=np.int64)
         timestamps = np.ascontiguousarray(timestamps, dtype=np.int64)
@@ -524,7 +563,14 @@ class GpuWindowOperator:
             key_hashes = np.ascontiguousarray(key_hashes, dtype=np.int32)
         if len(keys) != len(timestamps) or (values is not None and len(values) != len(keys)):
             raise ValueError("column lengths differ")
-        rc = N.lib().gw_ingest(self._h, len(keys), _ptr(keys), _ptr(key_hashes), _ptr(timestamps), _ptr(values))
+        if gaps is not None:
+            gaps = np.ascontiguousarray(gaps, dtype=np.int64)
+            if len(gaps) != len(keys):
+                raise ValueError("column lengths differ")
+            rc = N.lib().gw_ingest_gap(self._h, len(keys), _ptr(keys), _ptr(key_hashes), _ptr(timestamps),
+                                       _ptr(values), _ptr(gaps))
+        else:
+            rc = N.lib().gw_ingest(self._h, len(keys), _ptr(keys), _ptr(key_hashes), _ptr(timestamps), _ptr(values))
         N.check(rc, self._h)
 
     # first-element rows (flags=FLAG_FIRST_ELEMENT) ------------------------------------
@@ -638,8 +684,10 @@ class GpuWindowOperator:
         cols = (N.STAGE_VALUE if with_value else 0) | (N.STAGE_KEY_HASH if with_key_hash else 0)
         N.check(N.lib().gw_stage_send(self._h, int(slot), int(n), cols), self._h)
 
-    def process_batch_device(self, keys, timestamps, values=None, stream=None):
-        """Columns already in HBM (torch tensors or raw device pointers)."""
+    def process_batch_device(self, keys, timestamps, values=None, stream=None, gaps=None):
+        """Columns already in HBM (torch tensors or raw device pointers); gaps: the per-element
+        session gaps of a DynamicEventTimeSessionWindows operator."""
+        self._check_gaps(gaps)
         self._ensure_handle()
         def p(x):
             if x is None:
@@ -651,8 +699,14 @@ class GpuWindowOperator:
         if stream is None:  # the columns were produced on PyTorch's current stream
             import torch
             stream = torch.cuda.current_stream(keys.device).cuda_stream
-        rc = N.lib().gw_ingest_device(self._h, n, p(keys), None, p(timestamps), p(values),
-                                      ctypes.c_void_p(stream) if stream else None)
+        if gaps is not None:
+            if gaps.numel() != n:
+                raise ValueError("column lengths differ")
+            rc = N.lib().gw_ingest_gap_device(self._h, n, p(keys), None, p(timestamps), p(values), p(gaps),
+                                              ctypes.c_void_p(stream) if stream else None)
+        else:
+            rc = N.lib().gw_ingest_device(self._h, n, p(keys), None, p(timestamps), p(values),
+                                          ctypes.c_void_p(stream) if stream else None)
         N.check(rc, self._h)
 
     def process_batch_device_ptr(self, n: int, key_ptr: int, ts_ptr: int, val_ptr: Optional[int], stream=None):

@@ -72,8 +72,14 @@ typedef enum gw_assigner {
      * Rows are produced by gw_ingest* itself (CountTrigger fires on the element). */
     GW_COUNT_TUMBLING = 3, /* KeyedStream.countWindow(size): PurgingTrigger(CountTrigger(size))
                               (RS/api/datastream/KeyedStream.java:676-678)                  */
-    GW_COUNT_SLIDING  = 4  /* KeyedStream.countWindow(size, slide): CountEvictor(size) +
+    GW_COUNT_SLIDING  = 4, /* KeyedStream.countWindow(size, slide): CountEvictor(size) +
                               CountTrigger(slide) (KeyedStream.java:686-690)                */
+    /* DynamicEventTimeSessionWindows.withDynamicGap(extractor): element i gets the window
+     * [ts[i], ts[i] + gap[i]) from a gap column the caller evaluates the extractor into
+     * (gw_ingest_gap*).  gw_config.gap, size and slide are ignored.  Everything else is
+     * GW_SESSION: merging, lateness, triggers, the late side output, snapshots (a blob's
+     * header carries this assigner and gap 0; its body is the session body). */
+    GW_SESSION_DYNAMIC = 5
 } gw_assigner;
 
 typedef enum gw_trigger {
@@ -211,6 +217,19 @@ int  gw_stage_send(gw_handle* h, int32_t slot, int64_t n, int32_t cols);
  * caching allocator) without further synchronisation. */
 int  gw_ingest_device(gw_handle* h, int64_t n, const int64_t* d_key, const int32_t* d_key_hash,
                       const int64_t* d_ts, const void* d_value, void* stream);
+/* GW_SESSION_DYNAMIC handles: gw_ingest / gw_ingest_device plus the gap column, gap[i] > 0 the
+ * session gap of element i in ms (SessionWindowTimeGapExtractor.extract, evaluated by the
+ * caller).  A gap <= 0 fails the operator with GW_E_INVALID ("Dynamic session time gap must
+ * satisfy 0 < gap", DynamicEventTimeSessionWindows.assignWindows), ts + gap beyond int64 with
+ * GW_E_RANGE; like a Long.MIN_VALUE timestamp, either may surface at the next call on the
+ * handle, and every later call returns GW_E_STATE.  GW_E_INVALID: these calls on any other
+ * handle, gw_ingest / gw_ingest_device on a dynamic handle, a NULL gap column with n > 0.
+ * Not on a dynamic handle (GW_E_UNSUPPORTED): gw_stage_alloc (callers keep their own buffers
+ * and use these calls), gw_ingest_serialized*, gw_ingest_packed_device, gw_top_n_rows. */
+int  gw_ingest_gap(gw_handle* h, int64_t n, const int64_t* key, const int32_t* key_hash,
+                   const int64_t* ts, const void* value, const int64_t* gap);
+int  gw_ingest_gap_device(gw_handle* h, int64_t n, const int64_t* d_key, const int32_t* d_key_hash,
+                          const int64_t* d_ts, const void* d_value, const int64_t* d_gap, void* stream);
 /* Advance event time to wm: fire every window whose maxTimestamp (end-1) <= wm,
  * purge its state, and append the fired rows to the output.  *rows_fired (may be
  * NULL) receives the number of rows this call produced.  Watermarks that do not
@@ -439,11 +458,14 @@ void* gw_stream(gw_handle* h);
  * which = 4: *launches = those of them whose rows the flush's apply kernel emitted itself (the
  * fused fire: its time is part of which = 2, and which = 1 counts no launch for it), *ms = 0.
  * which = 5: *launches = the fused fires that were revoked (their rows dropped, the windows
- * fired the exact way instead), *ms = 0. */
+ * fired the exact way instead), *ms = 0.
+ * which = 6, 7, 8 (session handles, timing enabled with 2): the ingest's slot lookup (prep),
+ * grouping sort and per-key replay (segment), per launch; parts of which = 0. */
 int  gw_kernel_time_ms(gw_handle* h, int which, double* ms, int64_t* launches);
 /* enable: 0 off, 1 every launch, k > 1: the region path's pass 1 (one launch per batch, all
  * alike) is timed on every k-th batch only (two event records per timed launch cost host
- * time between batches); `launches` then counts the timed ones. */
+ * time between batches); `launches` then counts the timed ones.  Session handles: 2 also times
+ * the ingest's three stages by themselves (which = 6, 7, 8; six more event records per batch). */
 int  gw_enable_kernel_timing(gw_handle* h, int enable);
 
 /* ---- window stagger (stateless) ------------------------------------------ */

@@ -70,6 +70,7 @@ import org.apache.flink.api.common.state.KeyedStateStore;
 import org.apache.flink.streaming.api.functions.windowing.ProcessWindowFunction;
 import org.apache.flink.streaming.api.functions.windowing.WindowFunction;
 import org.apache.flink.streaming.api.operators.TimestampedCollector;
+import org.apache.flink.streaming.api.windowing.assigners.SessionWindowTimeGapExtractor;
 import org.apache.flink.streaming.api.windowing.assigners.WindowStagger;
 import org.apache.flink.streaming.api.windowing.windows.TimeWindow;
 import org.apache.flink.util.Collector;
@@ -118,8 +119,9 @@ public class GpuWindowOperator<IN, K>
     public enum OutputMode { POSITIONAL, MIN_MAX_BY, AGGREGATE, KEYED_WINDOW, WINDOW_FUNCTION }
 
     // gw_assigner / gw_trigger / gw_agg codes of include/gpuwin.h
-    private static final int GW_COUNT_TUMBLING = 3, GW_COUNT_SLIDING = 4;
-    private final int assigner, trigger, agg;
+    private static final int GW_SESSION = 2, GW_COUNT_TUMBLING = 3, GW_COUNT_SLIDING = 4, GW_SESSION_DYNAMIC = 5;
+    private int assigner;
+    private final int trigger, agg;
     private final OutputMode mode;
     private final long size, slide, offset, gap, lateness;
     private final KeySelector<IN, K> keySelector;
@@ -131,6 +133,7 @@ public class GpuWindowOperator<IN, K>
     private boolean byFirst = true;              // MIN_MAX_BY: the first of equal elements
     private WindowStagger stagger = WindowStagger.ALIGNED;  // tumbling only
     private ProcessWindowFunction<Object, Object, K, TimeWindow> windowFunction;  // WINDOW_FUNCTION
+    private SessionWindowTimeGapExtractor<IN> gapExtractor;  // DynamicEventTimeSessionWindows (null: a constant gap)
 
     private transient long handle;
     private transient ByteBuffer keys, keyHashes, ts, values, oKey, oStart, oEnd, oRes;
@@ -146,6 +149,7 @@ public class GpuWindowOperator<IN, K>
     // positional on Tuple3+: payload column (arrival sequence), the elements by sequence, and
     // per batch (sequence end, max timestamp) for releasing them
     private transient ByteBuffer payload, oPay;
+    private transient ByteBuffer gaps;  // dynamic-gap sessions: the extractor's value per record
     private transient ElementLog<IN> elements;
     private transient ArrayDeque<long[]> batches;
     private transient long batchMaxTs;
@@ -198,6 +202,23 @@ public class GpuWindowOperator<IN, K>
             throw new IllegalArgumentException("WindowStagger applies to TumblingEventTimeWindows only");
         }
         this.stagger = stagger;
+        return this;
+    }
+
+    /** DynamicEventTimeSessionWindows.withDynamicGap(extractor): on a session operator, every
+     *  element's window is [timestamp, timestamp + extractor.extract(element)).  The handle is
+     *  created as GW_SESSION_DYNAMIC (the constructor's gap is ignored); the extractor is
+     *  evaluated in processElement into a gap column beside the operator's own direct buffers
+     *  (the library's pinned slots do not carry one) and batches go through nativeIngestGap.
+     *  A gap <= 0 fails the task as the reference's assigner does ("Dynamic session time gap
+     *  must satisfy 0 < gap"), possibly at the next call after the batch. */
+    public GpuWindowOperator<IN, K> withDynamicGap(SessionWindowTimeGapExtractor<IN> extractor) {
+        if (assigner != GW_SESSION && assigner != GW_SESSION_DYNAMIC) {
+            throw new IllegalArgumentException("a session gap extractor applies to event-time session windows only");
+        }
+        if (extractor == null) throw new IllegalArgumentException("null session gap extractor");
+        this.gapExtractor = extractor;
+        this.assigner = GW_SESSION_DYNAMIC;
         return this;
     }
 
@@ -276,6 +297,7 @@ public class GpuWindowOperator<IN, K>
             batchMaxTs = Long.MIN_VALUE;
         }
         keys = direct(8); keyHashes = direct(4); ts = direct(8); values = direct(8);
+        if (gapExtractor != null) gaps = direct(8);
         oKey = direct(8); oStart = direct(8); oEnd = direct(8); oRes = direct(8);
         if (!handleDeferred) bindStaging();
         if (restored != null && handleDeferred) restored = null;  // staggered: the blobs hold no window state
@@ -326,7 +348,8 @@ public class GpuWindowOperator<IN, K>
      *  transfer of one batch overlaps the GPU work of the previous one.  Composite and
      *  first-element handles keep their own direct buffers (nativeIngest / nativeIngestPayload). */
     private void bindStaging() {
-        staged = !wide() && nativeStageAlloc(handle, 2, batchCapacity) == 0;
+        // (a dynamic-gap handle answers GW_E_UNSUPPORTED: not asked at all)
+        staged = !wide() && gapExtractor == null && nativeStageAlloc(handle, 2, batchCapacity) == 0;
         if (staged) bindSlot(0);
     }
 
@@ -509,6 +532,7 @@ public class GpuWindowOperator<IN, K>
         ts.putLong(n * 8, element.getTimestamp());
         if (doubleValue != null) values.putDouble(n * 8, doubleValue.applyAsDouble(v));
         else if (longValue != null) values.putLong(n * 8, longValue.applyAsLong(v));
+        if (gapExtractor != null) gaps.putLong(n * 8, gapExtractor.extract(v));
         if (wide()) {
             payload.putLong(n * 8, elements.append(v));
             batchMaxTs = Math.max(batchMaxTs, element.getTimestamp());
@@ -541,6 +565,8 @@ public class GpuWindowOperator<IN, K>
             nativeIngestStage(handle, slot, n, (doubleValue != null || longValue != null ? 1 /* GW_STAGE_VALUE */ : 0)
                     | (longKeys ? 0 : 2 /* GW_STAGE_KEY_HASH */));
             bindSlot(slot ^ 1);  // the other slot, once its previous transfer has read it
+        } else if (n > 0 && gapExtractor != null) {
+            nativeIngestGap(handle, n, keys, kh, ts, values, gaps);
         } else if (n > 0) {
             nativeIngest(handle, n, keys, kh, ts, values);
         }
@@ -739,6 +765,8 @@ public class GpuWindowOperator<IN, K>
                                             int subtask, int device, int flags, long capacityHint, long maxBatch);
     private static native void nativeIngest(long h, int n, ByteBuffer keys, ByteBuffer keyHashes, ByteBuffer ts,
                                             ByteBuffer values);
+    private static native void nativeIngestGap(long h, int n, ByteBuffer keys, ByteBuffer keyHashes, ByteBuffer ts,
+                                               ByteBuffer values, ByteBuffer gaps);
     private static native long nativeAdvanceWatermark(long h, long wm);
     private static native int nativeDrain(long h, ByteBuffer key, ByteBuffer start, ByteBuffer end, ByteBuffer result,
                                           int cap);

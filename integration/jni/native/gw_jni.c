@@ -56,10 +56,23 @@ JNIEXPORT void JNICALL CLS(nativeIngest)(JNIEnv* env, jclass c, jlong h, jint n,
     fail(env, (gw_handle*)(intptr_t)h, gw_ingest((gw_handle*)(intptr_t)h, n, k, kh, t, v));
 }
 
+/* DynamicEventTimeSessionWindows (GW_SESSION_DYNAMIC): nativeIngest plus the gap column the
+ * operator evaluated its SessionWindowTimeGapExtractor into (n little-endian longs). */
+JNIEXPORT void JNICALL CLS(nativeIngestGap)(JNIEnv* env, jclass c, jlong h, jint n, jobject keys, jobject keyHashes,
+                                            jobject ts, jobject values, jobject gaps) {
+    const int64_t* k = (*env)->GetDirectBufferAddress(env, keys);
+    const int32_t* kh = keyHashes ? (*env)->GetDirectBufferAddress(env, keyHashes) : 0;
+    const int64_t* t = (*env)->GetDirectBufferAddress(env, ts);
+    const void* v = values ? (*env)->GetDirectBufferAddress(env, values) : 0;
+    const int64_t* g = gaps ? (*env)->GetDirectBufferAddress(env, gaps) : 0;
+    fail(env, (gw_handle*)(intptr_t)h, gw_ingest_gap((gw_handle*)(intptr_t)h, n, k, kh, t, v, g));
+}
+
 /* Staged ingest (gw_stage_*): the operator's column buffers are the library's pinned slots, so
  * processElement writes each record straight into the memory the PCIe transfer reads.
- * nativeStageAlloc returns the status without throwing: GW_E_UNSUPPORTED (a composite or
- * first-element handle) leaves the operator on its own direct buffers and nativeIngest. */
+ * nativeStageAlloc returns the status without throwing: GW_E_UNSUPPORTED (a composite,
+ * first-element or dynamic-gap session handle) leaves the operator on its own direct buffers
+ * and nativeIngest / nativeIngestGap. */
 JNIEXPORT jint JNICALL CLS(nativeStageAlloc)(JNIEnv* env, jclass c, jlong h, jint slots, jint cap) {
     return gw_stage_alloc((gw_handle*)(intptr_t)h, slots, cap);
 }
