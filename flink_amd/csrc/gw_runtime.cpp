@@ -24,6 +24,7 @@
 #include <vector>
 #include <mutex>
 
+#include "gw_devmem.h"
 #include "gw_first.h"
 #include "gw_kernels.h"
 #include "gw_netbuf.h"
@@ -190,8 +191,8 @@ struct gw_handle {
     std::vector<gw_handle*> kids;
     bool shared_stream = false;      // the stream belongs to another handle
     int64_t cls_J = 0, cls_j = 0, cls_slide = 0, cls_off = 0;  // a child's class
-    int64_t *c_key = nullptr, *c_start = nullptr, *c_end = nullptr, *c_res = nullptr;
-    int64_t c_cap = 0, c_rows = 0, c_head = 0;
+    DevCols<5> c;  // key | start | end | result | payload (first-element handles only)
+    int64_t c_rows = 0, c_head = 0;
     // First-element handle (GW_FLAG_FIRST_ELEMENT, gw_first.hip): kids[0] folds the aggregate,
     // kids[1] the MIN of each record's arrival sequence; the payload log keeps every record's
     // payload (a ring indexed by sequence) until all windows that could hold it are cleaned.
@@ -202,11 +203,10 @@ struct gw_handle {
     int fe_cols = 1;                                    // log columns of fe_log_cap words each
     int64_t fe_restored_end = 0;                        // sequences below: restored elements
     int64_t fe_seq = 0;                                 // sequence of the next record
-    int64_t* fe_log = nullptr;
+    DevBuf<int64_t> fe_log;                             // fe_cols columns at stride fe_log_cap
     int64_t fe_log_cap = 0, fe_log_base = 0;            // live sequences [fe_log_base, fe_seq)
-    int64_t* fe_seqbuf = nullptr;
-    int64_t fe_seqbuf_cap = 0;
-    int64_t* fe_maxts = nullptr;                        // per batch (ring of kFeBatches): largest ts
+    DevBuf<int64_t> fe_seqbuf;
+    DevBuf<int64_t> fe_maxts;                           // per batch (ring of kFeBatches): largest ts
     struct FeBatch {
         int64_t seq_end;  // sequences of the batch end here
         int64_t slot;     // its max timestamp in fe_maxts[slot] until fetched
@@ -216,27 +216,23 @@ struct gw_handle {
     std::vector<FeBatch> fe_batches;  // not yet released, in arrival order
     int64_t fe_wm = INT64_MIN;        // the last watermark (release decisions)
     int64_t fe_batch_no = 0;
-    int64_t* c_pay = nullptr;
-    void* fe_scratch = nullptr;
-    size_t fe_scratch_bytes = 0;
-    int32_t* fe_bad = nullptr;
+    DevBuf<char> fe_scratch;
+    DevBuf<int32_t> fe_bad;
     static constexpr int64_t kFeBatches = 1 << 16;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;  // gw_ingest_device ordering with the producer stream
 
     // network-buffer ingest (gw_ingest_serialized*): grow-only device scratch, decoded
     // columns, watermark list, pinned status and staging for host bytes
-    void* nb_scratch = nullptr;
-    int64_t nb_scratch_cap = 0;
-    int64_t* nb_cols = nullptr;  // key | ts | value, nb_rec_cap each
-    int64_t nb_rec_cap = 0;
-    int64_t* nb_wm = nullptr;    // position | value, nb_wm_cap each
-    int64_t nb_wm_cap = 0;
-    NbStatus* d_nbst = nullptr;
-    NbStatus* h_nbst = nullptr;  // pinned
-    int64_t* h_nbwm = nullptr;   // pinned, 2 * kNbWmHost
-    uint8_t* h_nbbytes = nullptr;
-    uint8_t* d_nbbytes = nullptr;
-    int64_t nb_bytes_cap = 0;
+    DevBuf<char> nb_scratch;
+    DevBuf<int64_t> nb_cols;     // key | ts | value, nb_rec_cap() each
+    DevBuf<int64_t> nb_wm;       // position | value, nb_wm_cap() each
+    int64_t nb_rec_cap() const { return nb_cols.cap / 3; }
+    int64_t nb_wm_cap() const { return nb_wm.cap / 2; }
+    DevBuf<NbStatus> d_nbst;
+    PinnedBuf<NbStatus> h_nbst;
+    PinnedBuf<int64_t> h_nbwm;   // 2 * kNbWmHost
+    PinnedBuf<uint8_t> h_nbbytes;
+    DevBuf<uint8_t> d_nbbytes;
     static constexpr int64_t kNbWmHost = 4096;
     bool session = false;
 
@@ -248,19 +244,20 @@ struct gw_handle {
 
     // state table (region-major SoA, gw_kernels.h)
     PaneTable tv{};
+    DevBuf<int64_t> tv_mem;  // owns tv.base
     size_t table_bytes = 0;
 
     // Buffer of P1 tiles (k_rgn_p1) and the flush scratch (k_rgn_plan*, k_rgn_p2), sized
     // in 4096-record tiles; every array below holds buf_cap tiles' worth.
-    int64_t* e_col[6] = {};         // e_key e_a0 e_a1 (P2 output) p1_key p1_a0 p1_a1 (P1 output)
-    uint8_t* e_pos[2] = {};         // e_pos p1_pos
-    uint32_t* p1_row = nullptr;     // [tile][kPartBuckets]
-    uint32_t* p2_desc = nullptr;    // [bucket][tile]
-    int64_t* p2_off = nullptr;      // [blocks + 1], blocks = buckets x groups <= 2 tiles + kPartBuckets
-    int64_t* p2_roff = nullptr;
-    int64_t* rbeg = nullptr;        // [kPartBuckets + 1] rounds | [kPartBuckets + 1] records (bk_off)
-    uint32_t* r_row = nullptr;      // [rounds][kPartBuckets], rounds <= tiles + blocks
-    int64_t* r_base = nullptr;      // [rounds]
+    DevBuf<int64_t> e_col[6];       // e_key e_a0 e_a1 (P2 output) p1_key p1_a0 p1_a1 (P1 output)
+    DevBuf<uint8_t> e_pos[2];       // e_pos p1_pos
+    DevBuf<uint32_t> p1_row;        // [tile][kPartBuckets]
+    DevBuf<uint32_t> p2_desc;       // [bucket][tile]
+    DevBuf<int64_t> p2_off;         // [blocks + 1], blocks = buckets x groups <= 2 tiles + kPartBuckets
+    DevBuf<int64_t> p2_roff;
+    DevBuf<int64_t> rbeg;           // [kPartBuckets + 1] rounds | [kPartBuckets + 1] records (bk_off)
+    DevBuf<uint32_t> r_row;         // [rounds][kPartBuckets], rounds <= tiles + blocks
+    DevBuf<int64_t> r_base;         // [rounds]
     int64_t buf_cap = 0;            // tiles
     uint64_t stale_pos = 0;         // ring positions retired lazily, not yet cleaned (lazy_retire)
     static int64_t max_blocks(int64_t tiles) { return 2 * tiles + kPartBuckets + 1; }
@@ -280,10 +277,10 @@ struct gw_handle {
     // and leaves the newer ones in its P2 output, which the next flush applies from there.  Two
     // P2 output sets (key words, round rows, round bases, rbeg | bk_off) used in turn: eset is
     // the one the next P2 writes; while carry_on, set eset ^ 1 holds carry_mask's positions.
-    int64_t* e2_key = nullptr;
-    uint32_t* r_row2 = nullptr;
-    int64_t* r_base2 = nullptr;
-    int64_t* rbeg2 = nullptr;
+    DevBuf<int64_t> e2_key;
+    DevBuf<uint32_t> r_row2;
+    DevBuf<int64_t> r_base2;
+    DevBuf<int64_t> rbeg2;
     int64_t e2_cap = 0;             // tiles
     int eset = 0;
     bool carry_on = false;
@@ -295,17 +292,15 @@ struct gw_handle {
 
     // allowed lateness > 0 (tumbling / sliding): late records of fired, not yet cleaned
     // windows wait on the re-fire list until the next watermark (process_refire)
-    int64_t* rf[5] = {};            // key, pane, a0, a1, arrival number
-    int64_t rf_cap = 0;
+    DevCols<5> rf;                  // key, pane, a0, a1, arrival number
     int64_t rf_bound = 0;           // records ingested since the list was last processed
     int64_t seq_ctr = 0;            // arrival number of the next record
     int64_t rf_seq_base = 0;        // arrival number at the last processing
-    void* rf_sort = nullptr;        // sort keys / payloads / scratch
-    int64_t rf_sort_bytes = 0;
+    DevBuf<char> rf_sort;           // sort keys / payloads / scratch
 
     // late-data side output (GW_FLAG_LATE_SIDE_OUTPUT): key | ts | value, [lo_head, n_late_out) pending
-    int64_t* lo_buf[3] = {nullptr, nullptr, nullptr};
-    int64_t lo_cap = 0, lo_head = 0;
+    DevCols<3> lo_buf;
+    int64_t lo_head = 0;
     int64_t lo_bound = 0;  // records ingested since the buffer was last emptied (bounds n_late_out)
     bool late_out() const { return (cfg.flags & GW_FLAG_LATE_SIDE_OUTPUT) != 0; }
 
@@ -316,10 +311,7 @@ struct gw_handle {
     uint64_t occ = 0;  // ring positions that may hold data
 
     // deferred lists (double-buffered)
-    int64_t* dk[2] = {nullptr, nullptr};
-    int64_t* dp[2] = {nullptr, nullptr};
-    int64_t* da0[2] = {nullptr, nullptr};
-    int64_t* da1[2] = {nullptr, nullptr};
+    DevCols<4> def[2];  // key | pane | a0 | a1
     int64_t def_cap = 0;
     int cur = 0;
 
@@ -329,13 +321,13 @@ struct gw_handle {
     // copy stream into one of three device staging buffers used in turn, so the H2D of batches
     // b+1 and b+2 runs while batch b is aggregated, fired and drained.  A slot is refilled only after its H2D (ev_slot); a
     // device buffer is overwritten only after the ingest that read it (ev_dread).
-    std::vector<int64_t*> h_slot;
+    std::vector<PinnedBuf<int64_t>> h_slot;
     std::vector<hipEvent_t> ev_slot;
     std::vector<bool> slot_used;
     int64_t slot_cap = 0;
     int stage_next = 0;             // gw_ingest's next slot (of the first two)
     static constexpr int kStageBufs = 3;  // device buffers: up to two batches sent ahead of the ingest
-    int64_t* d_stage2[kStageBufs] = {};
+    DevBuf<int64_t> d_stage2[kStageBufs];
     hipEvent_t ev_dread[kStageBufs] = {};
     bool dread_valid[kStageBufs] = {};
     int dturn = 0;                  // the device buffer the next staged ingest reads
@@ -354,17 +346,13 @@ struct gw_handle {
     hipEvent_t ev_fork = nullptr;
 
     // output rows (device SoA), [rows_head, st.rows) pending
-    int64_t* o_key = nullptr;
-    int64_t* o_start = nullptr;
-    int64_t* o_end = nullptr;
-    int64_t* o_res = nullptr;
-    int64_t o_cap = 0;
+    DevCols<4> o;  // key | start | end | result
     int64_t rows_head = 0;
 
     // status
-    DevStatus* d_st = nullptr;
-    DevStatus* h_st = nullptr;
-    unsigned long long* d_tmp = nullptr;
+    DevBuf<DevStatus> d_st;
+    PinnedBuf<DevStatus> h_st;
+    DevBuf<unsigned long long> d_tmp;
 
     gw_stats stats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1};
     bool timing = false;
@@ -376,12 +364,12 @@ struct gw_handle {
     const uint64_t* pk_w = nullptr;
     int64_t pk_from = 0;
     gw_pack_geom pk_g{};
-    int64_t* pk_stage = nullptr;
+    DevBuf<int64_t> pk_stage;  // 3 columns of pk_stage_cap records
     int64_t pk_stage_cap = 0;
 
     SessionState* sess = nullptr;
     // key checks (gw_ingest* with key_hash, GW_FLAG_CHECK_KEY_GROUPS): device words, see k_check_keys
-    unsigned long long* d_chk = nullptr;
+    DevBuf<unsigned long long> d_chk;
     bool foreign_hash = false;  // a key_hash differed from Long.hashCode(key) (keys are caller ids)
     int ingest_unroll = 2;  // records per thread per iteration of k_ingest (GW_INGEST_UNROLL)
     int64_t region_min_batch = 1 << 16;  // smallest batch for the region path (GW_REGION_MIN_BATCH)
@@ -414,7 +402,7 @@ struct gw_handle {
     // the stream carries no event or copy between them.  h_st then lags by the last
     // batches (`lazy`): decisions that need exact counters call refresh().
     static constexpr int kAsync = 3;  // slots in flight: absorb the one 2 batches old
-    DevStatus* h_st_async[kAsync] = {};
+    PinnedBuf<DevStatus> h_st_async[kAsync];
     uint64_t async_seq[kAsync] = {};
     uint64_t pub_ctr = 0;
     bool async_pending[kAsync] = {};
@@ -524,7 +512,7 @@ struct gw_handle {
     // Write one scalar status word, ordered on the stream (no host sync).
     int set_field(size_t off, unsigned long long v) {
         hgen++;
-        *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h_st) + off) = v;
+        *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h_st.p) + off) = v;
         HIPCHECK(launch_status_set(d_st, (int)(off / 8), v, -1, stream));
         return GW_OK;
     }
@@ -589,36 +577,33 @@ struct gw_handle {
         t.nreg = (int64_t)t.nsub << t.rb1;
         t.cap = t.nreg << l2s;
     }
-    int alloc_table(PaneTable& t, int64_t want) {
+    int alloc_table(PaneTable& t, DevBuf<int64_t>& mem, int64_t want) {
         t = tv;
         table_geometry(t, want);
         const int64_t S = pt_S(t);
         t.mask_shift = t.ring <= 8 ? 0 : t.ring <= 16 ? 1 : t.ring <= 32 ? 2 : 3;
         t.region_words = S + pt_mask_words(t) + S * (int64_t)t.ring * t.words;
-        HIPCHECK(hipMalloc((void**)&t.base, pane_table_bytes(t)));
+        HIPCHECK(mem.reserve_discard((int64_t)(pane_table_bytes(t) / 8)));
+        t.base = mem;
         HIPCHECK(launch_table_init(t, stream));
         return GW_OK;
     }
-    void free_region() {
-        for (void** p : {(void**)&e2_key, (void**)&r_row2, (void**)&r_base2, (void**)&rbeg2}) {
-            if (*p) hipFree(*p);
-            *p = nullptr;
-        }
+    void free_eset2() {
+        e2_key.reset(); r_row2.reset(); r_base2.reset(); rbeg2.reset();
         e2_cap = 0;
+    }
+    void free_region() {
+        free_eset2();
         eset = 0;
-        for (auto& p : e_col) { if (p) hipFree(p); p = nullptr; }
-        for (auto& p : e_pos) { if (p) hipFree(p); p = nullptr; }
-        for (void** p : {(void**)&p1_row, (void**)&p2_desc, (void**)&p2_off, (void**)&p2_roff, (void**)&r_row,
-                         (void**)&r_base}) {
-            if (*p) hipFree(*p);
-            *p = nullptr;
-        }
+        for (auto& b : e_col) b.reset();
+        for (auto& b : e_pos) b.reset();
+        p1_row.reset(); p2_desc.reset(); p2_off.reset(); p2_roff.reset(); r_row.reset(); r_base.reset();
         buf_cap = 0;
     }
     // Region buffer of >= need tiles (re-allocated to `want` tiles when too small; only
     // with no segment waiting).
     int ensure_region(int64_t need, int64_t want) {
-        if (!rbeg) HIPCHECK(hipMalloc((void**)&rbeg, (size_t)2 * (kPartBuckets + 1) * 8));  // rbeg | bk_off
+        HIPCHECK(rbeg.reserve_discard(2 * (kPartBuckets + 1)));  // rbeg | bk_off
         if (need <= buf_cap) return GW_OK;
         if (carry_on) {  // the carried records live in the buffers about to be re-allocated
             int rc = flush_buffer();
@@ -626,35 +611,31 @@ struct gw_handle {
         }
         if (nseg) return fail(GW_E_STATE, "internal: region buffer re-allocated with %d segments waiting", nseg);
         const int64_t cap = std::max(need, want);
-        const size_t recs = (size_t)cap * kPartTile;
+        const int64_t recs = cap * kPartTile;
         hipStreamSynchronize(stream);
         free_region();
         for (int i = 0; i < 6; ++i) {
             if ((i == 2 || i == 5) && tv.words != 2) continue;  // a1 only for AVG
-            HIPCHECK(hipMalloc((void**)&e_col[i], recs * 8));
+            HIPCHECK(e_col[i].reserve_discard(recs));
         }
-        for (auto& p : e_pos) HIPCHECK(hipMalloc((void**)&p, recs));
-        HIPCHECK(hipMalloc((void**)&p1_row, (size_t)cap * kPartBuckets * 4));
-        HIPCHECK(hipMalloc((void**)&p2_desc, (size_t)cap * kPartBuckets * 4));
-        HIPCHECK(hipMalloc((void**)&p2_off, (size_t)max_blocks(cap) * 8));
-        HIPCHECK(hipMalloc((void**)&p2_roff, (size_t)max_blocks(cap) * 8));
-        HIPCHECK(hipMalloc((void**)&r_row, (size_t)max_rounds(cap) * kPartBuckets * 4));
-        HIPCHECK(hipMalloc((void**)&r_base, (size_t)max_rounds(cap) * 8));
+        for (auto& b : e_pos) HIPCHECK(b.reserve_discard(recs));
+        HIPCHECK(p1_row.reserve_discard(cap * kPartBuckets));
+        HIPCHECK(p2_desc.reserve_discard(cap * kPartBuckets));
+        HIPCHECK(p2_off.reserve_discard(max_blocks(cap)));
+        HIPCHECK(p2_roff.reserve_discard(max_blocks(cap)));
+        HIPCHECK(r_row.reserve_discard(max_rounds(cap) * kPartBuckets));
+        HIPCHECK(r_base.reserve_discard(max_rounds(cap)));
         buf_cap = cap;
         return GW_OK;
     }
     // The second P2 output set (nar2 carry), as large as the first.
     int ensure_eset2() {
         if (e2_cap == buf_cap && e2_key) return GW_OK;
-        for (void** p : {(void**)&e2_key, (void**)&r_row2, (void**)&r_base2, (void**)&rbeg2}) {
-            if (*p) hipFree(*p);
-            *p = nullptr;
-        }
-        const size_t recs = (size_t)buf_cap * kPartTile;
-        HIPCHECK(hipMalloc((void**)&e2_key, recs * 8));
-        HIPCHECK(hipMalloc((void**)&r_row2, (size_t)max_rounds(buf_cap) * kPartBuckets * 4));
-        HIPCHECK(hipMalloc((void**)&r_base2, (size_t)max_rounds(buf_cap) * 8));
-        HIPCHECK(hipMalloc((void**)&rbeg2, (size_t)2 * (kPartBuckets + 1) * 8));
+        free_eset2();
+        HIPCHECK(e2_key.reserve_discard(buf_cap * kPartTile));
+        HIPCHECK(r_row2.reserve_discard(max_rounds(buf_cap) * kPartBuckets));
+        HIPCHECK(r_base2.reserve_discard(max_rounds(buf_cap)));
+        HIPCHECK(rbeg2.reserve_discard(2 * (kPartBuckets + 1)));
         e2_cap = buf_cap;
         return GW_OK;
     }
@@ -664,62 +645,28 @@ struct gw_handle {
         // stream, whose few values beyond the narrow record's 28 bits defer and grow the list
         // over a fire cycle), so the list grows in few steps
         int64_t nc = std::max<int64_t>(need + need / 2, 1 << 16);
-        for (int b = 0; b < 2; ++b) {
-            int64_t* nk; int64_t* np; int64_t* n0; int64_t* n1;
-            HIPCHECK(hipMalloc((void**)&nk, nc * 8));
-            HIPCHECK(hipMalloc((void**)&np, nc * 8));
-            HIPCHECK(hipMalloc((void**)&n0, nc * 8));
-            HIPCHECK(hipMalloc((void**)&n1, nc * 8));
-            if (dk[b] && b == cur) {
-                // a lagging status does not know the last batch's entries: copy them all
-                const int64_t used = lazy ? def_cap : (int64_t)h_st->n_deferred;
-                if (used) {
-                    HIPCHECK(hipMemcpyAsync(nk, dk[b], used * 8, hipMemcpyDeviceToDevice, stream));
-                    HIPCHECK(hipMemcpyAsync(np, dp[b], used * 8, hipMemcpyDeviceToDevice, stream));
-                    HIPCHECK(hipMemcpyAsync(n0, da0[b], used * 8, hipMemcpyDeviceToDevice, stream));
-                    HIPCHECK(hipMemcpyAsync(n1, da1[b], used * 8, hipMemcpyDeviceToDevice, stream));
-                }
-            }
-            if (dk[b]) {
-                hipStreamSynchronize(stream);
-                hipFree(dk[b]); hipFree(dp[b]); hipFree(da0[b]); hipFree(da1[b]);
-            }
-            dk[b] = nk; dp[b] = np; da0[b] = n0; da1[b] = n1;
-        }
+        // a lagging status does not know the last batch's entries: copy them all
+        const int64_t used = lazy ? def_cap : (int64_t)h_st->n_deferred;
+        for (int b = 0; b < 2; ++b) HIPCHECK(def[b].reserve_keep(nc, 0, b == cur ? used : 0, stream));
         def_cap = nc;
         return GW_OK;
     }
     int ensure_output(int64_t need) {  // need = total rows (pending + new)
-        if (need <= o_cap) return GW_OK;
-        int64_t nc = std::max<int64_t>(need + need / 4, 1 << 16);
-        int64_t* nb[4];
-        for (int i = 0; i < 4; ++i) HIPCHECK(hipMalloc((void**)&nb[i], nc * 8));
-        const int64_t used = (int64_t)h_st->rows;
-        int64_t* old[4] = {o_key, o_start, o_end, o_res};
-        for (int i = 0; i < 4; ++i) {
-            if (old[i]) {
-                if (used) HIPCHECK(hipMemcpyAsync(nb[i], old[i], used * 8, hipMemcpyDeviceToDevice, stream));
-                hipStreamSynchronize(stream);
-                hipFree(old[i]);
-            }
-        }
-        o_key = nb[0]; o_start = nb[1]; o_end = nb[2]; o_res = nb[3];
-        o_cap = nc;
+        if (need <= o.cap) return GW_OK;
+        const int64_t nc = std::max<int64_t>(need + need / 4, 1 << 16);
+        HIPCHECK(o.reserve_keep(nc, 0, (int64_t)h_st->rows, stream));
         return GW_OK;
     }
     void free_stage() {
         if (cstream) hipStreamSynchronize(cstream);
         hipStreamSynchronize(stream);
-        for (size_t i = 0; i < h_slot.size(); ++i) {
-            if (h_slot[i]) hipHostFree(h_slot[i]);
-            if (ev_slot[i]) hipEventDestroy(ev_slot[i]);
-        }
+        for (auto ev : ev_slot)
+            if (ev) hipEventDestroy(ev);
         h_slot.clear();
         ev_slot.clear();
         slot_used.clear();
         for (int t = 0; t < kStageBufs; ++t) {
-            if (d_stage2[t]) hipFree(d_stage2[t]);
-            d_stage2[t] = nullptr;
+            d_stage2[t].reset();
             dread_valid[t] = false;
             pre_valid[t] = false;
         }
@@ -758,13 +705,13 @@ struct gw_handle {
         }
         for (int t = 0; t < kStageBufs; ++t) {
             if (!ev_dread[t]) HIPCHECK(hipEventCreateWithFlags(&ev_dread[t], hipEventDisableTiming));
-            HIPCHECK(hipMalloc((void**)&d_stage2[t], (size_t)cap * 28));
+            HIPCHECK(d_stage2[t].reserve_discard((cap * 28 + 7) / 8));
         }
-        h_slot.assign(ns, nullptr);
+        h_slot.resize(ns);
         ev_slot.assign(ns, nullptr);
         slot_used.assign(ns, false);
         for (int i = 0; i < ns; ++i) {
-            HIPCHECK(hipHostMalloc((void**)&h_slot[i], (size_t)cap * 28, hipHostMallocDefault));
+            HIPCHECK(h_slot[i].alloc((cap * 28 + 7) / 8, hipHostMallocDefault));
             HIPCHECK(hipEventCreateWithFlags(&ev_slot[i], hipEventDisableTiming));
         }
         slot_cap = cap;
@@ -773,7 +720,7 @@ struct gw_handle {
     // Fired rows to caller memory (any host memory, e.g. a JVM direct ByteBuffer): large
     // drains go through two pinned bounce chunks -- the D2H of chunk j+1 runs while chunk j is
     // copied out by several threads -- instead of one pageable copy per column.
-    int64_t* h_bounce = nullptr;
+    PinnedBuf<int64_t> h_bounce;
     hipEvent_t ev_bounce[2] = {nullptr, nullptr};
     static constexpr int64_t kBounceRows = (int64_t)1 << 21;  // per chunk and column (16 MB)
     static bool host_pinned(const void* p) {
@@ -801,7 +748,7 @@ struct gw_handle {
             return GW_OK;
         }
         if (!h_bounce) {
-            HIPCHECK(hipHostMalloc((void**)&h_bounce, (size_t)2 * 4 * kBounceRows * 8, hipHostMallocDefault));
+            HIPCHECK(h_bounce.alloc(2 * 4 * kBounceRows, hipHostMallocDefault));
             for (auto& ev : ev_bounce) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
         const int64_t nch = (c + kBounceRows - 1) / kBounceRows;
@@ -840,14 +787,15 @@ struct gw_handle {
     // Re-hash the live slots into a table of `new_cap` slots (drops dead keys).
     int rehash(int64_t new_cap) {
         PaneTable nt;
-        int rc = alloc_table(nt, new_cap);
+        DevBuf<int64_t> nmem;
+        int rc = alloc_table(nt, nmem, new_cap);
         if (rc) return rc;
         if ((rc = zero_shards(1))) return rc;                          // ins (used slots)
         if (h_st->flags & GW_DF_TABLE_FULL)
             if ((rc = zero_shards(2))) return rc;                      // flags
         HIPCHECK(launch_rehash(tv, nt, d_st, stream));
         HIPCHECK(hipStreamSynchronize(stream));
-        HIPCHECK(hipFree(tv.base));
+        tv_mem = std::move(nmem);
         tv = nt;
         table_bytes = pane_table_bytes(nt);
         stats.rehashes++;
@@ -897,13 +845,13 @@ struct gw_handle {
             if ((rc = ensure_deferred(nin))) return rc;
             if ((rc = set_field(offsetof(DevStatus, n_deferred), 0))) return rc;
             MergeArgs a{};
-            a.i_key = dk[cur]; a.i_pane = dp[cur]; a.i_a0 = da0[cur]; a.i_a1 = da1[cur];
+            a.i_key = def[cur][0]; a.i_pane = def[cur][1]; a.i_a0 = def[cur][2]; a.i_a1 = def[cur][3];
             a.n = nin;
             a.b = (int64_t)B;
             a.b_pos = (int32_t)pos_of(B);
             a.t = tv;
             const int o = cur ^ 1;
-            a.d_key = dk[o]; a.d_pane = dp[o]; a.d_a0 = da0[o]; a.d_a1 = da1[o];
+            a.d_key = def[o][0]; a.d_pane = def[o][1]; a.d_a0 = def[o][2]; a.d_a1 = def[o][3];
             a.st = d_st;
             if ((rc = clean_stale())) return rc;
             HIPCHECK(launch_merge_deferred(a, stream));
@@ -919,40 +867,18 @@ struct gw_handle {
     }
 
     int ensure_refire(int64_t need) {
-        if (need <= rf_cap) return GW_OK;
+        if (need <= rf.cap) return GW_OK;
         const int64_t nc = std::max<int64_t>(need + need / 2, 1 << 16);
-        const int64_t used = std::min(rf_bound, rf_cap);
-        for (int c = 0; c < 5; ++c) {
-            int64_t* nb;
-            HIPCHECK(hipMalloc((void**)&nb, nc * 8));
-            if (rf[c] && used) HIPCHECK(hipMemcpyAsync(nb, rf[c], used * 8, hipMemcpyDeviceToDevice, stream));
-            if (rf[c]) {
-                HIPCHECK(hipStreamSynchronize(stream));
-                hipFree(rf[c]);
-            }
-            rf[c] = nb;
-        }
-        rf_cap = nc;
+        HIPCHECK(rf.reserve_keep(nc, 0, std::min(rf_bound, rf.cap), stream));
         return GW_OK;
     }
 
     int ensure_late(int64_t need) {
-        if (need <= lo_cap) return GW_OK;
+        if (need <= lo_buf.cap) return GW_OK;
         int rc;
         if ((rc = refresh())) return rc;  // exact n_late_out before copying
-        const int64_t used = (int64_t)h_st->n_late_out;
         const int64_t nc = std::max<int64_t>(need + need / 2, 1 << 16);
-        for (int c = 0; c < 3; ++c) {
-            int64_t* nb;
-            HIPCHECK(hipMalloc((void**)&nb, nc * 8));
-            if (lo_buf[c] && used) HIPCHECK(hipMemcpyAsync(nb, lo_buf[c], used * 8, hipMemcpyDeviceToDevice, stream));
-            if (lo_buf[c]) {
-                HIPCHECK(hipStreamSynchronize(stream));
-                hipFree(lo_buf[c]);
-            }
-            lo_buf[c] = nb;
-        }
-        lo_cap = nc;
+        HIPCHECK(lo_buf.reserve_keep(nc, 0, (int64_t)h_st->n_late_out, stream));
         return GW_OK;
     }
 
@@ -989,12 +915,11 @@ struct gw_handle {
             const int seq_bits = span < ((int64_t)1 << 32) ? 32 : 64;
             const int64_t kb = ((nrf * 8 + 255) / 256) * 256, vb = ((nrf * 4 + 255) / 256) * 256;
             const int64_t need = 2 * kb + 2 * vb + radix_sort_scratch_bytes(nrf);
-            if (need > rf_sort_bytes) {
-                if (rf_sort) { HIPCHECK(hipStreamSynchronize(stream)); hipFree(rf_sort); }
-                HIPCHECK(hipMalloc(&rf_sort, need + need / 2));
-                rf_sort_bytes = need + need / 2;
+            if (need > rf_sort.cap) {
+                if (rf_sort) HIPCHECK(hipStreamSynchronize(stream));
+                HIPCHECK(rf_sort.reserve_discard(need + need / 2));
             }
-            char* base = (char*)rf_sort;
+            char* base = rf_sort;
             uint64_t* k0 = (uint64_t*)base;
             uint64_t* k1 = (uint64_t*)(base + kb);
             uint32_t* v0 = (uint32_t*)(base + 2 * kb);
@@ -1029,7 +954,7 @@ struct gw_handle {
             r.offset = cfg.offset;
             r.slide = slide();
             r.size = size();
-            r.o_key = o_key; r.o_start = o_start; r.o_end = o_end; r.o_res = o_res;
+            r.o_key = o[0]; r.o_start = o[1]; r.o_end = o[2]; r.o_res = o[3];
             r.st = d_st;
             if ((rc = rows_reset_now())) return rc;
             HIPCHECK(launch_refire(r, stream));
@@ -1041,7 +966,7 @@ struct gw_handle {
             a.b = (int64_t)B;
             a.b_pos = (int32_t)pos_of(B);
             a.t = tv;
-            a.d_key = dk[cur]; a.d_pane = dp[cur]; a.d_a0 = da0[cur]; a.d_a1 = da1[cur];
+            a.d_key = def[cur][0]; a.d_pane = def[cur][1]; a.d_a0 = def[cur][2]; a.d_a1 = def[cur][3];
             a.st = d_st;
             if ((rc = clean_stale())) return rc;
             HIPCHECK(launch_merge_deferred(a, stream));
@@ -1112,7 +1037,7 @@ struct gw_handle {
         if (!nd) return GW_OK;
         int rc;
         if ((rc = set_field(offsetof(DevStatus, def_min_pane), (unsigned long long)INT64_MAX))) return rc;
-        HIPCHECK(launch_deferred_min(dp[cur], nd, d_st, stream));
+        HIPCHECK(launch_deferred_min(def[cur][1], nd, d_st, stream));
         if ((rc = refresh())) return rc;
         out = (i128)h_st->def_min_pane;
         return GW_OK;
@@ -1139,7 +1064,7 @@ struct gw_handle {
                     return rc;
                 e.t = tv;
                 e.emask = emask;
-                e.d_key = dk[cur]; e.d_pane = dp[cur]; e.d_a0 = da0[cur]; e.d_a1 = da1[cur];
+                e.d_key = def[cur][0]; e.d_pane = def[cur][1]; e.d_a0 = def[cur][2]; e.d_a1 = def[cur][3];
                 e.st = d_st;
                 HIPCHECK(launch_evict(e, stream));
                 occ &= ~emask;
@@ -1232,7 +1157,7 @@ struct gw_handle {
                 return rc;
             if ((rc = ensure_output((int64_t)h_st->rows + (int64_t)f.nwin * ((int64_t)h_st->used_slots + 1))))
                 return rc;
-            f.o_key = o_key; f.o_start = o_start; f.o_end = o_end; f.o_res = o_res;
+            f.o_key = o[0]; f.o_start = o[1]; f.o_end = o[2]; f.o_res = o[3];
             lazy_retire(f);
             if ((rc = fire_launch(f))) return rc;
             fired(f, k_last, keep);
@@ -1284,7 +1209,7 @@ struct gw_handle {
             const i128 gl = (i128)wm - (i128)cfg.allowed_lateness;
             a.gap_late = gl < (i128)INT64_MIN ? INT64_MIN : (int64_t)gl;
         }
-        a.d_key = dk[cur]; a.d_pane = dp[cur]; a.d_a0 = da0[cur]; a.d_a1 = da1[cur];
+        a.d_key = def[cur][0]; a.d_pane = def[cur][1]; a.d_a0 = def[cur][2]; a.d_a1 = def[cur][3];
         a.st = d_st;
         // panes up to the last one of the last fired window re-fire (lateness > 0)
         if (late_out() && exact) {
@@ -1447,11 +1372,11 @@ struct gw_handle {
             a.f_wmask = f.wmask[0];
             a.f_start = f.start0;
             a.f_end = f.start0 + f.size;
-            a.o_key = o_key; a.o_start = o_start; a.o_end = o_end; a.o_res = o_res;
-            a.o_cap = o_cap;
+            a.o_key = o[0]; a.o_start = o[1]; a.o_end = o[2]; a.o_res = o[3];
+            a.o_cap = o.cap;
             // what is knowable before the apply: room for a row per key seen so far, nothing
             // deferred, no leftovers of an earlier flush
-            FireGuard g{0, o_cap, 1, rows_reset_pending ? 1 : 0};
+            FireGuard g{0, o.cap, 1, rows_reset_pending ? 1 : 0};
             rows_reset_pending = false;  // the guard zeroes the cursor
             HIPCHECK(launch_fire_guard(d_st, g, stream));
         }
@@ -1502,10 +1427,9 @@ struct gw_handle {
     int pk_materialize(int64_t nrec, const int64_t*& key, const int64_t*& ts, const int64_t*& val) {
         if (nrec > pk_stage_cap) {
             HIPCHECK(hipStreamSynchronize(stream));
-            hipFree(pk_stage);
-            pk_stage = nullptr;
             const int64_t c = std::max<int64_t>(nrec + nrec / 4, 1 << 16);
-            HIPCHECK(hipMalloc((void**)&pk_stage, (size_t)c * 3 * 8));
+            pk_stage_cap = 0;
+            HIPCHECK(pk_stage.reserve_discard(c * 3));
             pk_stage_cap = c;
         }
         int64_t* k = pk_stage;
@@ -1674,7 +1598,7 @@ struct gw_handle {
     int check_keys(int64_t nrec, const int64_t* d_key, const int32_t* d_hash) {
         const bool range = (cfg.flags & GW_FLAG_CHECK_KEY_GROUPS) != 0;
         if (nrec == 0 || (!d_hash && !range)) return GW_OK;
-        if (!d_chk) HIPCHECK(hipMalloc((void**)&d_chk, 32));
+        HIPCHECK(d_chk.reserve_discard(4));
         const unsigned long long init[4] = {0ull, ~0ull, 0ull, 0ull};
         HIPCHECK(hipMemcpyAsync(d_chk, init, 32, hipMemcpyHostToDevice, stream));
         const int32_t mp = cfg.max_parallelism, p = cfg.parallelism, ix = cfg.operator_index;
@@ -1708,10 +1632,12 @@ struct gw_handle {
 
     // ------------------------------------------------- key -> Java hashCode (KeyHashMap)
     KeyHashMap khm{};
+    DevBuf<int64_t> khm_key;   // own khm.key / khm.hash
+    DevBuf<int32_t> khm_hash;
     int64_t khm_used = 0;  // keys in khm
     void khm_free() {
-        if (khm.key) hipFree(khm.key);
-        if (khm.hash) hipFree(khm.hash);
+        khm_key.reset();
+        khm_hash.reset();
         khm = KeyHashMap{};
         khm_used = 0;
     }
@@ -1721,21 +1647,21 @@ struct gw_handle {
         int64_t cap = khm.cap ? khm.cap : 1 << 12;
         while (2 * (khm_used + more) > cap) cap *= 2;
         KeyHashMap n;
-        n.cap = cap;
-        if (hipMalloc((void**)&n.key, (size_t)(cap + 1) * 8) != hipSuccess ||
-            hipMalloc((void**)&n.hash, (size_t)(cap + 1) * 4) != hipSuccess) {
-            if (n.key) hipFree(n.key);
+        DevBuf<int64_t> nkey;
+        DevBuf<int32_t> nhash;
+        if (nkey.reserve_discard(cap + 1) != hipSuccess || nhash.reserve_discard(cap + 1) != hipSuccess)
             return fail(GW_E_OOM, "key-hash map: out of device memory");
-        }
+        n.cap = cap;
+        n.key = nkey;
+        n.hash = nhash;
         HIPCHECK(launch_fill64(n.key, cap, kEmptyKey, stream));
         HIPCHECK(hipMemsetAsync(n.key + cap, 0, 8, stream));
         HIPCHECK(hipMemsetAsync(n.hash + cap, 0, 4, stream));
         if (khm.cap) HIPCHECK(launch_khmap_rehash(khm, n, stream));
         HIPCHECK(hipStreamSynchronize(stream));
-        const int64_t used = khm_used;
-        khm_free();
+        khm_key = std::move(nkey);
+        khm_hash = std::move(nhash);
         khm = n;
-        khm_used = used;
         return GW_OK;
     }
     // Host copy of the map, sorted by key, for key groups at snapshot time.
@@ -1772,11 +1698,11 @@ struct gw_handle {
         if (!n) return GW_OK;
         int rc = khm_reserve(n);
         if (rc) return rc;
-        int64_t* dk_ = nullptr;
-        int32_t* dh_ = nullptr;
-        if (!d_chk) HIPCHECK(hipMalloc((void**)&d_chk, 32));
-        HIPCHECK(hipMalloc((void**)&dk_, (size_t)n * 8));
-        HIPCHECK(hipMalloc((void**)&dh_, (size_t)n * 4));
+        DevBuf<int64_t> dk_;
+        DevBuf<int32_t> dh_;
+        HIPCHECK(d_chk.reserve_discard(4));
+        HIPCHECK(dk_.reserve_discard(n));
+        HIPCHECK(dh_.reserve_discard(n));
         HIPCHECK(hipMemcpy(dk_, keys.data(), (size_t)n * 8, hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(dh_, hashes.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         const unsigned long long init[4] = {0ull, ~0ull, 0ull, 0ull};
@@ -1786,8 +1712,6 @@ struct gw_handle {
         unsigned long long out[4];
         HIPCHECK(hipMemcpyAsync(out, d_chk, 32, hipMemcpyDeviceToHost, stream));
         HIPCHECK(hipStreamSynchronize(stream));
-        hipFree(dk_);
-        hipFree(dh_);
         khm_used += (int64_t)out[2];
         if (out[3]) return fail(GW_E_INVALID, "snapshot: a key with two different key hashes");
         return GW_OK;
@@ -1838,9 +1762,9 @@ struct gw_handle {
         uint32_t flags;
     };
     std::vector<OvEntry> ov_pending;  // restored, not yet on the device
-    int64_t* d_ov = nullptr;          // key | k | a0 | a1, ov_n each
-    uint32_t* d_ov_flags = nullptr;
-    int32_t* d_ov_head = nullptr;     // [tv.cap + 1]
+    DevBuf<int64_t> d_ov;             // key | k | a0 | a1, ov_n each
+    DevBuf<uint32_t> d_ov_flags;
+    DevBuf<int32_t> d_ov_head;        // [tv.cap + 1]
     int64_t ov_n = 0, ov_nkeys = 0;
     i128 ov_max_k = 0;
     std::vector<int64_t> ov_timer_ks;  // sorted window indices with a pending timer
@@ -1856,18 +1780,14 @@ struct gw_handle {
         return o;
     }
     void ov_free() {
-        if (d_ov) hipFree(d_ov);
-        if (d_ov_flags) hipFree(d_ov_flags);
-        if (d_ov_head) hipFree(d_ov_head);
-        d_ov = nullptr; d_ov_flags = nullptr; d_ov_head = nullptr;
+        d_ov.reset(); d_ov_flags.reset(); d_ov_head.reset();
         ov_n = ov_nkeys = 0;
         ov_timer_ks.clear();
     }
     // Slots of the overlay keys in the current table (after the restore and every rehash).
     int ov_attach() {
         if (!ov_n) return GW_OK;
-        if (d_ov_head) HIPCHECK(hipFree(d_ov_head));
-        HIPCHECK(hipMalloc((void**)&d_ov_head, (size_t)(tv.cap + 1) * 4));
+        HIPCHECK(d_ov_head.reserve_discard(tv.cap + 1));
         HIPCHECK(hipMemsetAsync(d_ov_head, 0xff, (size_t)(tv.cap + 1) * 4, stream));
         HIPCHECK(launch_overlay_attach(tv, ov_view(), d_ov_head, d_st, stream));
         dirty = true;
@@ -1910,8 +1830,8 @@ struct gw_handle {
         ov_timer_ks.erase(std::unique(ov_timer_ks.begin(), ov_timer_ks.end()), ov_timer_ks.end());
         ov_pending.clear();
         if (!n) return GW_OK;
-        HIPCHECK(hipMalloc((void**)&d_ov, (size_t)n * 32));
-        HIPCHECK(hipMalloc((void**)&d_ov_flags, (size_t)n * 4));
+        HIPCHECK(d_ov.reserve_discard(n * 4));
+        HIPCHECK(d_ov_flags.reserve_discard(n));
         HIPCHECK(hipMemcpy(d_ov, cols.data(), (size_t)n * 32, hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_ov_flags, fl.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         ov_n = n;
@@ -2020,13 +1940,14 @@ struct gw_handle {
         std::vector<int64_t> col[4];
         std::vector<int32_t> kgs;
         if (bound > 0) {
-            int64_t* d = nullptr;
-            HIPCHECK(hipMalloc((void**)&d, (size_t)bound * 36));
+            DevBuf<char> dmem;
+            HIPCHECK(dmem.reserve_discard(bound * 36));
+            int64_t* d = (int64_t*)dmem.p;
             SnapArgs a{};
             a.t = tv;
             a.occ = occ;
             for (i128 p = B; p < B + R; ++p) a.pane_of_pos[pos_of(p)] = (int64_t)p;
-            a.d_key = dk[cur]; a.d_pane = dp[cur]; a.d_a0 = da0[cur]; a.d_a1 = da1[cur];
+            a.d_key = def[cur][0]; a.d_pane = def[cur][1]; a.d_a0 = def[cur][2]; a.d_a1 = def[cur][3];
             a.n_def = n_def;
             a.max_p = cfg.max_parallelism;
             a.kg_lo = hashed ? 0 : kg_lo;  // hashed keys: every entry, key groups on the host
@@ -2047,7 +1968,6 @@ struct gw_handle {
                 }
                 if (n && e == hipSuccess) e = hipMemcpy(kgs.data(), a.o_kg, n * 4, hipMemcpyDeviceToHost);
             }
-            hipFree(d);
             if (e != hipSuccess) return fail(GW_E_DEVICE, "snapshot: %s", hipGetErrorString(e));
             if (hashed) {  // key groups from the keys' own hashes, then the range filter
                 size_t w = 0;
@@ -2581,11 +2501,11 @@ struct gw_handle {
         FireArgs f{};
         i128 keep;
         if ((rc = fire_args(k_first, kt, (kt + 1) * m, f, keep))) return rc;
-        f.o_key = o_key; f.o_start = o_start; f.o_end = o_end; f.o_res = o_res;
+        f.o_key = o[0]; f.o_start = o[1]; f.o_end = o[2]; f.o_res = o[3];
         f.guarded = 1;
         lazy_retire(f);
         if (fuse && launched) {
-            FireGuard g2{0, o_cap, 1, 0, 1};
+            FireGuard g2{0, o.cap, 1, 0, 1};
             HIPCHECK(launch_fire_guard(d_st, g2, stream));
             HIPCHECK(launch_fire_retire(f, stream));
             dirty = true;
@@ -2605,7 +2525,7 @@ struct gw_handle {
             stale_pos = stale0;
             return flush_post(pf);
         }
-        FireGuard g{0, o_cap, (int64_t)f.nwin, rows_reset_pending ? 1 : 0};
+        FireGuard g{0, o.cap, (int64_t)f.nwin, rows_reset_pending ? 1 : 0};
         rows_reset_pending = false;  // the guard zeroes the cursor
         HIPCHECK(launch_fire_guard(d_st, g, stream));
         if ((rc = fire_launch(f))) return rc;
@@ -2849,8 +2769,7 @@ static int make_first_element(gw_handle* h) {
     h->fe = true;
     h->stream = h->kids[0]->stream;
     h->shared_stream = true;
-    if (hipMalloc((void**)&h->fe_maxts, (size_t)gw_handle::kFeBatches * 8) != hipSuccess ||
-        hipMalloc((void**)&h->fe_bad, 4) != hipSuccess) {
+    if (h->fe_maxts.reserve_discard(gw_handle::kFeBatches) != hipSuccess || h->fe_bad.reserve_discard(1) != hipSuccess) {
         g_create_error = "first-element buffers: out of device memory";
         return GW_E_OOM;
     }
@@ -2886,15 +2805,14 @@ int gw_create(const gw_config* cfg, gw_handle** out) {
     if ((e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming)) != hipSuccess)
         return bail(GW_E_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(e));
-    if ((e = hipMalloc((void**)&h->d_st, sizeof(DevStatus))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_tmp, 64)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&h->h_st, sizeof(DevStatus), hipHostMallocDefault)) != hipSuccess)
+    if ((e = h->d_st.reserve_discard(1)) != hipSuccess || (e = h->d_tmp.reserve_discard(8)) != hipSuccess ||
+        (e = h->h_st.alloc(1, hipHostMallocDefault)) != hipSuccess)
         return bail(GW_E_DEVICE, std::string("status alloc: ") + hipGetErrorString(e));
     hipMemset(h->d_st, 0, sizeof(DevStatus));
     memset(h->h_st, 0, sizeof(DevStatus));
     for (int i = 0; i < gw_handle::kAsync; ++i) {
         // coherent: the device's stores reach the host without a cache flush on either side
-        if ((e = hipHostMalloc((void**)&h->h_st_async[i], sizeof(DevStatus), hipHostMallocCoherent)) != hipSuccess)
+        if ((e = h->h_st_async[i].alloc(1, hipHostMallocCoherent)) != hipSuccess)
             return bail(GW_E_DEVICE, std::string("status alloc: ") + hipGetErrorString(e));
         memset(h->h_st_async[i], 0, sizeof(DevStatus));
     }
@@ -2966,7 +2884,7 @@ int gw_create(const gw_config* cfg, gw_handle** out) {
     h->div = make_udiv((uint64_t)h->g);
     h->fired_k = h->k_for_wm(INT64_MIN) + 1;
     h->B = h->fired_k * h->m;
-    rc = h->alloc_table(h->tv, std::max<int64_t>(1024, (int64_t)((double)hint / gw_handle::kTableLoad) + 1));
+    rc = h->alloc_table(h->tv, h->tv_mem, std::max<int64_t>(1024, (int64_t)((double)hint / gw_handle::kTableLoad) + 1));
     if (rc) return bail(rc, h->err);
     h->table_bytes = gw_handle::pane_table_bytes(h->tv);
     rc = h->ensure_deferred(1 << 16);
@@ -2985,52 +2903,14 @@ int gw_destroy(gw_handle* h) {
         for (size_t j = h->kids.size(); j-- > 0;) gw_destroy(h->kids[j]);  // child 0 owns the stream
         h->kids.clear();
         h->stream = nullptr;
-        if (h->c_key) { hipFree(h->c_key); hipFree(h->c_start); hipFree(h->c_end); hipFree(h->c_res); }
-        if (h->c_pay) hipFree(h->c_pay);
-        if (h->fe_log) hipFree(h->fe_log);
-        if (h->fe_seqbuf) hipFree(h->fe_seqbuf);
-        if (h->fe_maxts) hipFree(h->fe_maxts);
-        if (h->fe_bad) hipFree(h->fe_bad);
-        if (h->fe_scratch) hipFree(h->fe_scratch);
     }
     h->hp.dump();
     if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->pk_stage) hipFree(h->pk_stage);
-    h->khm_free();
     if (h->sess) session_destroy(h->sess);
-    h->ov_free();
-    if (h->tv.base) hipFree(h->tv.base);
-    for (int b = 0; b < 2; ++b) {
-        if (h->dk[b]) { hipFree(h->dk[b]); hipFree(h->dp[b]); hipFree(h->da0[b]); hipFree(h->da1[b]); }
-    }
-    if (h->o_key) { hipFree(h->o_key); hipFree(h->o_start); hipFree(h->o_end); hipFree(h->o_res); }
-    for (int c = 0; c < 5; ++c)
-        if (h->rf[c]) hipFree(h->rf[c]);
-    for (int c = 0; c < 3; ++c)
-        if (h->lo_buf[c]) hipFree(h->lo_buf[c]);
-    if (h->rf_sort) hipFree(h->rf_sort);
-    h->free_stage();
-    h->free_region();
-    if (h->rbeg) hipFree(h->rbeg);
-    if (h->d_st) hipFree(h->d_st);
-    if (h->d_tmp) hipFree(h->d_tmp);
-    if (h->h_st) hipHostFree(h->h_st);
-    for (int i = 0; i < gw_handle::kAsync; ++i)
-        if (h->h_st_async[i]) hipHostFree(h->h_st_async[i]);
+    h->free_stage();  // waits for the copy stream, destroys the slots' events
     h->t_ingest.destroy();
     h->t_fire.destroy();
     h->t_apply.destroy();
-    if (h->d_chk) hipFree(h->d_chk);
-    if (h->nb_scratch) hipFree(h->nb_scratch);
-    if (h->nb_cols) hipFree(h->nb_cols);
-    if (h->nb_wm) hipFree(h->nb_wm);
-    if (h->d_nbst) hipFree(h->d_nbst);
-    if (h->h_nbst) hipHostFree(h->h_nbst);
-    if (h->h_nbwm) hipHostFree(h->h_nbwm);
-    if (h->h_nbbytes) hipHostFree(h->h_nbbytes);
-    if (h->d_nbbytes) hipFree(h->d_nbbytes);
-    h->free_stage();
-    if (h->h_bounce) hipHostFree(h->h_bounce);
     for (auto ev : h->ev_bounce)
         if (ev) hipEventDestroy(ev);
     for (int t = 0; t < gw_handle::kStageBufs; ++t)
@@ -3043,8 +2923,10 @@ int gw_destroy(gw_handle* h) {
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_in) hipEventDestroy(h->ev_in);
     if (h->ev_out) hipEventDestroy(h->ev_out);
-    if (h->stream && !h->shared_stream) hipStreamDestroy(h->stream);
+    // the buffers go with the handle: after the last synchronise, before the stream
+    hipStream_t own = h->shared_stream ? nullptr : h->stream;
     delete h;
+    if (own) hipStreamDestroy(own);
     return GW_OK;
 }
 
@@ -3094,41 +2976,24 @@ static int kid_rc(gw_handle* h, gw_handle* kid, int rc) {
     } while (0)
 
 // ---- first-element handle (GW_FLAG_FIRST_ELEMENT, gw_first.hip) ----------------------
-// Row buffers of the joined rows (key, start, end, result, payload) for `need` rows in all.
-static int fe_reserve_rows(gw_handle* h, int64_t need) {
-    if (need <= h->c_cap) return GW_OK;
-    const int64_t cap = std::max<int64_t>(need, 2 * h->c_cap);
-    int64_t* nb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 5; ++q) {
-        if (hipMalloc((void**)&nb[q], (size_t)cap * 8) != hipSuccess) {
-            for (int r = 0; r < q; ++r) hipFree(nb[r]);
-            return h->fail(GW_E_OOM, "first-element row buffer: out of device memory");
-        }
-    }
-    int64_t* old[5] = {h->c_key, h->c_start, h->c_end, h->c_res, h->c_pay};
+// Room for `need` waiting rows in all in c (the columns in `mask`): the live rows [c_head, c_rows)
+// move to the front.  First-element handles join into all five columns, a window-class
+// composite gathers into the first four.
+static int reserve_rows(gw_handle* h, int64_t need, unsigned mask, const char* what) {
+    if (need <= h->c.cap) return GW_OK;
     const int64_t live = h->c_rows - h->c_head;
-    for (int q = 0; q < 5; ++q)
-        if (old[q] && live) hipMemcpyAsync(nb[q], old[q] + h->c_head, live * 8, hipMemcpyDeviceToDevice, h->stream);
-    hipStreamSynchronize(h->stream);
-    for (int q = 0; q < 5; ++q)
-        if (old[q]) hipFree(old[q]);
-    h->c_key = nb[0]; h->c_start = nb[1]; h->c_end = nb[2]; h->c_res = nb[3]; h->c_pay = nb[4];
-    h->c_cap = cap;
+    const hipError_t e = h->c.reserve_keep(std::max<int64_t>(need, 2 * h->c.cap), h->c_head, live, h->stream, mask);
+    if (e != hipSuccess) return h->fail(GW_E_OOM, "%s: %s", what, hipGetErrorString(e));
     h->c_rows = live;
     h->c_head = 0;
     return GW_OK;
 }
+static int fe_reserve_rows(gw_handle* h, int64_t need) { return reserve_rows(h, need, 0x1f, "first-element row buffer"); }
 
 static int fe_reserve_scratch(gw_handle* h, size_t need) {
-    if (need <= h->fe_scratch_bytes) return GW_OK;
-    if (h->fe_scratch) {
-        hipStreamSynchronize(h->stream);
-        hipFree(h->fe_scratch);
-    }
-    h->fe_scratch = nullptr;
-    h->fe_scratch_bytes = 0;
-    if (hipMalloc(&h->fe_scratch, need) != hipSuccess) return h->fail(GW_E_OOM, "first-element join scratch");
-    h->fe_scratch_bytes = need;
+    if ((int64_t)need <= h->fe_scratch.cap) return GW_OK;
+    if (h->fe_scratch) hipStreamSynchronize(h->stream);
+    if (h->fe_scratch.reserve_discard((int64_t)need) != hipSuccess) return h->fail(GW_E_OOM, "first-element join scratch");
     return GW_OK;
 }
 
@@ -3146,7 +3011,7 @@ static int by_select(gw_handle* h, int64_t n, const int64_t* key, const int64_t*
         e = fe_by_select(n, key, start, res, h->fe_log, h->fe_log_cap, h->fe_log_base, h->fe_seq, h->fe_restored_end,
                          h->cfg.offset, slide, h->cfg.size, h->fe_by_last, f64,
                          h->cfg.agg == GW_MAX_I64 || h->cfg.agg == GW_MAX_F64, o_seq, o_pay, h->fe_scratch,
-                         h->fe_scratch_bytes, h->fe_bad, h->stream);
+                         (size_t)h->fe_scratch.cap, h->fe_bad, h->stream);
     int32_t bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, h->fe_bad, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -3172,11 +3037,11 @@ static int fe_gather(gw_handle* h) {
         if ((rc = fe_reserve_rows(h, h->c_rows + na))) return rc;
         const int64_t o = h->c_rows;
         const int64_t* src[4] = {ak, as, ae, (const int64_t*)ar};
-        int64_t* dst[4] = {h->c_key + o, h->c_start + o, h->c_end + o, h->c_res + o};
+        int64_t* dst[4] = {h->c[0] + o, h->c[1] + o, h->c[2] + o, h->c[3] + o};
         for (int q = 0; q < 4; ++q)
             if (hipMemcpyAsync(dst[q], src[q], (size_t)na * 8, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
                 return h->fail(GW_E_DEVICE, "minBy / maxBy rows");
-        if ((rc = by_select(h, na, ak, as, (const int64_t*)ar, nullptr, h->c_pay + o))) return rc;
+        if ((rc = by_select(h, na, ak, as, (const int64_t*)ar, nullptr, h->c[4] + o))) return rc;
         h->c_rows += na;
         if ((rc = gw_clear_rows(A))) return kid_rc(h, A, rc);
         return GW_OK;
@@ -3202,8 +3067,8 @@ static int fe_gather(gw_handle* h) {
         hipError_t e = hipMemsetAsync(h->fe_bad, 0, 4, h->stream);
         if (e == hipSuccess)
             e = fe_join(na, ak, as, ae, (const int64_t*)ar, bk, bs, (const int64_t*)br, h->fe_log, h->fe_log_base,
-                        h->fe_log_cap, h->c_key + o, h->c_start + o, h->c_end + o, h->c_res + o, h->c_pay + o,
-                        h->fe_scratch, h->fe_scratch_bytes, h->fe_bad, h->stream);
+                        h->fe_log_cap, h->c[0] + o, h->c[1] + o, h->c[2] + o, h->c[3] + o, h->c[4] + o,
+                        h->fe_scratch, (size_t)h->fe_scratch.cap, h->fe_bad, h->stream);
         int32_t bad = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, h->fe_bad, 4, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -3268,17 +3133,16 @@ static int fe_log_reserve(gw_handle* h, int64_t n) {
     const int64_t need = h->fe_seq + n - h->fe_log_base;
     if (need > h->fe_log_cap) {
         const int64_t ncap = std::max<int64_t>(2 * need, 1 << 20);
-        int64_t* nl = nullptr;
-        if (hipMalloc((void**)&nl, (size_t)ncap * 8 * h->fe_cols) != hipSuccess) return h->fail(GW_E_OOM, "payload log");
+        DevBuf<int64_t> nl;
+        if (nl.reserve_discard(ncap * h->fe_cols) != hipSuccess) return h->fail(GW_E_OOM, "payload log");
         hipError_t e = hipSuccess;
         for (int c = 0; c < h->fe_cols && h->fe_log && e == hipSuccess; ++c)  // column c at c * cap
             e = fe_log_regrow(h->fe_log + c * h->fe_log_cap, h->fe_log_cap, nl + c * ncap, ncap, h->fe_log_base,
                               h->fe_seq, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (h->fe_log) hipFree(h->fe_log);
-        h->fe_log = nl;
-        h->fe_log_cap = ncap;
         if (e != hipSuccess) return h->fail(GW_E_DEVICE, "payload log: %s", hipGetErrorString(e));
+        h->fe_log = std::move(nl);
+        h->fe_log_cap = ncap;
     }
     return GW_OK;
 }
@@ -3298,13 +3162,9 @@ int gw_ingest_payload_device(gw_handle* h, int64_t n, const int64_t* d_key, cons
     }
     if (n == 0) return GW_OK;
     // arrival sequence of the batch's records (kids[1] folds its minimum per window)
-    if (n > h->fe_seqbuf_cap) {
+    if (n > h->fe_seqbuf.cap) {
         hipStreamSynchronize(s);
-        if (h->fe_seqbuf) hipFree(h->fe_seqbuf);
-        h->fe_seqbuf = nullptr;
-        h->fe_seqbuf_cap = 0;
-        if (hipMalloc((void**)&h->fe_seqbuf, (size_t)n * 8) != hipSuccess) return h->fail(GW_E_OOM, "sequence buffer");
-        h->fe_seqbuf_cap = n;
+        if (h->fe_seqbuf.reserve_discard(n) != hipSuccess) return h->fail(GW_E_OOM, "sequence buffer");
     }
     hipError_t e = h->fe_by ? hipSuccess : fe_iota64(h->fe_seqbuf, n, h->fe_seq, s);
     if (e == hipSuccess) {
@@ -3346,13 +3206,10 @@ int gw_ingest_payload(gw_handle* h, int64_t n, const int64_t* key, const int32_t
     if (n == 0) return GW_OK;
     hipSetDevice(h->cfg.device);
     // host columns: one device copy of each (synchronous), then the device path
-    int64_t* d = nullptr;
-    int32_t* dh = nullptr;
-    if (hipMalloc((void**)&d, (size_t)n * 32) != hipSuccess) return h->fail(GW_E_OOM, "payload staging");
-    if (key_hash && hipMalloc((void**)&dh, (size_t)n * 4) != hipSuccess) {
-        hipFree(d);
+    DevBuf<int64_t> d;
+    DevBuf<int32_t> dh;
+    if (d.reserve_discard(n * 4) != hipSuccess || (key_hash && dh.reserve_discard(n) != hipSuccess))
         return h->fail(GW_E_OOM, "payload staging");
-    }
     hipError_t e = hipMemcpyAsync(d, key, n * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + n, ts, n * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * n, value, n * 8, hipMemcpyHostToDevice, h->stream);
@@ -3361,8 +3218,6 @@ int gw_ingest_payload(gw_handle* h, int64_t n, const int64_t* key, const int32_t
     int rc = e == hipSuccess ? gw_ingest_payload_device(h, n, d, dh, d + n, d + 2 * n, d + 3 * n, h->stream)
                              : h->fail(GW_E_DEVICE, "H2D: %s", hipGetErrorString(e));
     hipStreamSynchronize(h->stream);
-    hipFree(d);
-    if (dh) hipFree(dh);
     return rc;
 }
 
@@ -3375,7 +3230,7 @@ int gw_drain_payload(gw_handle* h, int64_t* key, int64_t* start, int64_t* end, v
     if (c > 0) {
         const int64_t o = h->c_head;
         int64_t* dst[5] = {key, start, end, (int64_t*)result, payload};
-        int64_t* src[5] = {h->c_key, h->c_start, h->c_end, h->c_res, h->c_pay};
+        int64_t* src[5] = {h->c[0], h->c[1], h->c[2], h->c[3], h->c[4]};
         hipError_t e = hipSuccess;
         for (int q = 0; q < 5 && e == hipSuccess; ++q)
             if (dst[q]) e = hipMemcpyAsync(dst[q], src[q] + o, c * 8, hipMemcpyDeviceToHost, h->stream);
@@ -3582,13 +3437,10 @@ int gw_ingest_gap(gw_handle* h, int64_t n, const int64_t* key, const int32_t* ke
     if (n == 0) return GW_OK;
     hipSetDevice(h->cfg.device);
     const int ncol = value ? 4 : 3;
-    int64_t* d = nullptr;
-    int32_t* dh = nullptr;
-    if (hipMalloc((void**)&d, (size_t)n * 8 * ncol) != hipSuccess) return h->fail(GW_E_OOM, "gap ingest staging");
-    if (key_hash && hipMalloc((void**)&dh, (size_t)n * 4) != hipSuccess) {
-        hipFree(d);
+    DevBuf<int64_t> d;
+    DevBuf<int32_t> dh;
+    if (d.reserve_discard(n * ncol) != hipSuccess || (key_hash && dh.reserve_discard(n) != hipSuccess))
         return h->fail(GW_E_OOM, "gap ingest staging");
-    }
     hipError_t e = hipMemcpyAsync(d, key, n * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + n, ts, n * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * n, gap, n * 8, hipMemcpyHostToDevice, h->stream);
@@ -3598,8 +3450,6 @@ int gw_ingest_gap(gw_handle* h, int64_t n, const int64_t* key, const int32_t* ke
                        ? ingest_device_cols(h, n, d, dh, d + n, value ? d + 3 * n : nullptr, d + 2 * n, h->stream)
                        : h->fail(GW_E_DEVICE, "H2D: %s", hipGetErrorString(e));
     hipStreamSynchronize(h->stream);  // the staging is read; a record error surfaces at the next call
-    hipFree(d);
-    if (dh) hipFree(dh);
     return rc;
 }
 
@@ -3674,10 +3524,9 @@ int gw_ingest_packed_device(gw_handle* h, int64_t n_other, const int64_t* d_key,
         if (n > h->pk_stage_cap) {
             hipStreamSynchronize((hipStream_t)stream);
             hipStreamSynchronize(h->stream);
-            hipFree(h->pk_stage);
-            h->pk_stage = nullptr;
             const int64_t c = std::max<int64_t>(n + n / 4, 1 << 16);
-            if (hipMalloc((void**)&h->pk_stage, (size_t)c * 3 * 8) != hipSuccess)
+            h->pk_stage_cap = 0;
+            if (h->pk_stage.reserve_discard(c * 3) != hipSuccess)
                 return h->fail(GW_E_OOM, "packed staging: out of device memory");
             h->pk_stage_cap = c;
         }
@@ -3764,18 +3613,16 @@ int gw_decode_serialized(const void* d_bytes, int64_t nbytes, const gw_record_la
         return GW_E_INVALID;
     }
     hipStream_t s = (hipStream_t)stream;
-    void* scratch = nullptr;
-    NbStatus* d_st = nullptr;
+    DevBuf<char> scratch;
+    DevBuf<NbStatus> d_st;
     NbStatus hst{};
-    hipError_t e = hipMalloc(&scratch, (size_t)nb_scratch_bytes(nbytes));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_st, sizeof(NbStatus));
+    hipError_t e = scratch.reserve_discard(nb_scratch_bytes(nbytes));
+    if (e == hipSuccess) e = d_st.reserve_discard(1);
     if (e == hipSuccess)
         e = launch_nb_decode((const uint8_t*)d_bytes, nbytes, L, d_key, d_ts, d_value, rec_cap, d_wm_pos, d_wm_val,
                              wm_cap, scratch, d_st, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&hst, d_st, sizeof(NbStatus), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (scratch) hipFree(scratch);
-    if (d_st) hipFree(d_st);
     if (e != hipSuccess) { g_create_error = std::string("decode: ") + hipGetErrorString(e); return GW_E_DEVICE; }
     out->records = hst.records;
     out->watermarks = hst.watermarks;
@@ -3787,25 +3634,15 @@ int gw_decode_serialized(const void* d_bytes, int64_t nbytes, const gw_record_la
 }
 
 static int nb_ensure(gw_handle* h, int64_t nbytes, const NbLayout& L) {
-    auto grow = [&](void** p, int64_t& cap, int64_t want, int64_t unit) -> hipError_t {
-        if (want <= cap) return hipSuccess;
-        if (*p) hipFree(*p);
-        *p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(p, (size_t)(want * unit));
-        if (e == hipSuccess) cap = want;
-        return e;
-    };
     const int64_t want = std::max<int64_t>(nbytes, 1 << 16);
     // upper bounds: every element a record without timestamp / a watermark
     const int64_t recs = want / (4 + 1 + L.vbytes) + 1, wms = want / 13 + 1;
-    hipError_t e = grow(&h->nb_scratch, h->nb_scratch_cap, nb_scratch_bytes(want), 1);
-    if (e == hipSuccess) e = grow((void**)&h->nb_cols, h->nb_rec_cap, recs, 24);
-    if (e == hipSuccess) e = grow((void**)&h->nb_wm, h->nb_wm_cap, wms, 16);
-    if (e == hipSuccess && !h->d_nbst) e = hipMalloc((void**)&h->d_nbst, sizeof(NbStatus));
-    if (e == hipSuccess && !h->h_nbst) e = hipHostMalloc((void**)&h->h_nbst, sizeof(NbStatus), hipHostMallocDefault);
-    if (e == hipSuccess && !h->h_nbwm)
-        e = hipHostMalloc((void**)&h->h_nbwm, 2 * gw_handle::kNbWmHost * 8, hipHostMallocDefault);
+    hipError_t e = h->nb_scratch.reserve_discard(nb_scratch_bytes(want));
+    if (e == hipSuccess) e = h->nb_cols.reserve_discard(3 * recs);
+    if (e == hipSuccess) e = h->nb_wm.reserve_discard(2 * wms);
+    if (e == hipSuccess) e = h->d_nbst.reserve_discard(1);
+    if (e == hipSuccess && !h->h_nbst) e = h->h_nbst.alloc(1, hipHostMallocDefault);
+    if (e == hipSuccess && !h->h_nbwm) e = h->h_nbwm.alloc(2 * gw_handle::kNbWmHost, hipHostMallocDefault);
     if (e != hipSuccess) return h->fail(GW_E_OOM, "network-buffer scratch: %s", hipGetErrorString(e));
     return GW_OK;
 }
@@ -3819,12 +3656,12 @@ static int nb_ingest_on_stream(gw_handle* h, const uint8_t* d_bytes, int64_t nby
     int rc = nb_ensure(h, nbytes, L);
     if (rc) return rc;
     int64_t* k = h->nb_cols;
-    int64_t* t = h->nb_cols + h->nb_rec_cap;
-    int64_t* v = h->nb_cols + 2 * h->nb_rec_cap;
+    int64_t* t = h->nb_cols + h->nb_rec_cap();
+    int64_t* v = h->nb_cols + 2 * h->nb_rec_cap();
     int64_t* wp = h->nb_wm;
-    int64_t* wv = h->nb_wm + h->nb_wm_cap;
-    hipError_t e = launch_nb_decode(d_bytes, nbytes, L, k, t, L.val_type ? v : nullptr, h->nb_rec_cap, wp, wv,
-                                    h->nb_wm_cap, h->nb_scratch, h->d_nbst, h->stream);
+    int64_t* wv = h->nb_wm + h->nb_wm_cap();
+    hipError_t e = launch_nb_decode(d_bytes, nbytes, L, k, t, L.val_type ? v : nullptr, h->nb_rec_cap(), wp, wv,
+                                    h->nb_wm_cap(), h->nb_scratch, h->d_nbst, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbst, h->d_nbst, sizeof(NbStatus), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbwm, wp, gw_handle::kNbWmHost * 8, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess)
@@ -3849,7 +3686,7 @@ static int nb_ingest_on_stream(gw_handle* h, const uint8_t* d_bytes, int64_t nby
         if (e == hipSuccess) e = hipMemcpy(wval.data(), wv, nw * 8, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return h->fail(GW_E_DEVICE, "watermark list: %s", hipGetErrorString(e));
     } else {
-        wpos.assign(h->h_nbwm, h->h_nbwm + nw);
+        wpos.assign(h->h_nbwm.p, h->h_nbwm + nw);
         wval.assign(h->h_nbwm + gw_handle::kNbWmHost, h->h_nbwm + gw_handle::kNbWmHost + nw);
     }
     int64_t fired = 0, done = 0;
@@ -3936,16 +3773,12 @@ int gw_ingest_serialized(gw_handle* h, const void* bytes, int64_t nbytes, const 
     if (rows_fired) *rows_fired = 0;
     if (nbytes == 0) return GW_OK;
     hipSetDevice(h->cfg.device);
-    if (nbytes > h->nb_bytes_cap) {
-        if (h->h_nbbytes) { hipHostFree(h->h_nbbytes); hipFree(h->d_nbbytes); }
-        h->h_nbbytes = nullptr;
-        h->d_nbbytes = nullptr;
-        h->nb_bytes_cap = 0;
+    if (nbytes > h->d_nbbytes.cap) {  // (the device buffer is the last to be allocated)
         const int64_t cap = std::max<int64_t>(nbytes, 1 << 20);
-        hipError_t e = hipHostMalloc((void**)&h->h_nbbytes, (size_t)cap, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_nbbytes, (size_t)cap);
+        h->d_nbbytes.reset();
+        hipError_t e = h->h_nbbytes.alloc(cap, hipHostMallocDefault);
+        if (e == hipSuccess) e = h->d_nbbytes.reserve_discard(cap);
         if (e != hipSuccess) return h->fail(GW_E_OOM, "network-buffer staging: %s", hipGetErrorString(e));
-        h->nb_bytes_cap = cap;
     }
     // the previous call synchronised the stream, so the pinned staging is free
     memcpy(h->h_nbbytes, bytes, (size_t)nbytes);
@@ -4204,8 +4037,8 @@ static int fe_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, in
     std::vector<int64_t> pays(h->fe_by ? by_key.size() : seqs.size());
     if (h->fe_by && !by_key.empty()) {
         const size_t m = by_key.size();
-        int64_t* d = nullptr;
-        HIPCHECK_H(h, hipMalloc((void**)&d, m * 32));
+        DevBuf<int64_t> d;
+        HIPCHECK_H(h, d.reserve_discard((int64_t)m * 4));
         hipError_t e = hipMemcpyAsync(d, by_key.data(), m * 8, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d + m, by_start.data(), m * 8, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * m, by_res.data(), m * 8, hipMemcpyHostToDevice, h->stream);
@@ -4213,19 +4046,17 @@ static int fe_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, in
                                  : h->fail(GW_E_DEVICE, "minBy / maxBy snapshot: %s", hipGetErrorString(e));
         if (rc == GW_OK && hipMemcpy(pays.data(), d + 3 * m, m * 8, hipMemcpyDeviceToHost) != hipSuccess)
             rc = h->fail(GW_E_DEVICE, "minBy / maxBy snapshot");
-        hipFree(d);
         if (rc) return rc;
     }
     if (!seqs.empty()) {
         for (int64_t q : seqs)
             if (q < h->fe_log_base || q >= h->fe_seq) return h->fail(GW_E_STATE, "first-element snapshot: payload released");
-        int64_t* d = nullptr;
-        HIPCHECK_H(h, hipMalloc((void**)&d, seqs.size() * 16));
+        DevBuf<int64_t> d;
+        HIPCHECK_H(h, d.reserve_discard((int64_t)seqs.size() * 2));
         hipError_t e = hipMemcpyAsync(d, seqs.data(), seqs.size() * 8, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = fe_log_gather(h->fe_log, h->fe_log_cap, d, (int64_t)seqs.size(), d + seqs.size(), h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(pays.data(), d + seqs.size(), seqs.size() * 8, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        hipFree(d);
         if (e != hipSuccess) return h->fail(GW_E_DEVICE, "first-element snapshot: %s", hipGetErrorString(e));
     }
     // pass 2: the blob
@@ -4309,15 +4140,14 @@ static int fe_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
     const int64_t m = (int64_t)pays.size();
     if (m) {
         if ((rc = fe_log_reserve(h, m))) return rc;
-        int64_t* d = nullptr;
-        HIPCHECK_H(h, hipMalloc((void**)&d, (size_t)m * 8 * h->fe_cols));
+        DevBuf<int64_t> d;
+        HIPCHECK_H(h, d.reserve_discard(m * h->fe_cols));
         hipError_t e = hipMemcpy(d, pays.data(), (size_t)m * 8, hipMemcpyHostToDevice);
         for (int c = 1; c < h->fe_cols && e == hipSuccess; ++c)
             e = hipMemcpy(d + c * m, by_cols[c - 1].data(), (size_t)m * 8, hipMemcpyHostToDevice);
         for (int c = 0; c < h->fe_cols && e == hipSuccess; ++c)
             e = fe_log_append(h->fe_log + c * h->fe_log_cap, h->fe_log_cap, h->fe_seq, d + c * m, m, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        hipFree(d);
         if (e != hipSuccess) return h->fail(GW_E_DEVICE, "first-element restore: %s", hipGetErrorString(e));
         h->fe_seq += m;
         if (h->fe_by) h->fe_restored_end = h->fe_seq;  // restored elements stand for their own window
@@ -4495,7 +4325,7 @@ static void rows_view(gw_handle* h, int64_t** k, int64_t** s, int64_t** e, int64
     if (h->session) {
         session_rows(h->sess, k, s, e, r, total);
     } else {
-        *k = h->o_key; *s = h->o_start; *e = h->o_end; *r = h->o_res;
+        *k = h->o[0]; *s = h->o[1]; *e = h->o[2]; *r = h->o[3];
         *total = (int64_t)h->h_st->rows;
     }
 }
@@ -4536,11 +4366,11 @@ int gw_drain(gw_handle* h, int64_t* key, int64_t* start, int64_t* end, void* res
         if (c > 0) {
             hipError_t e = hipSuccess;
             const int64_t o = h->c_head;
-            if (key) e = hipMemcpyAsync(key, h->c_key + o, c * 8, hipMemcpyDeviceToHost, h->stream);
-            if (start && e == hipSuccess) e = hipMemcpyAsync(start, h->c_start + o, c * 8, hipMemcpyDeviceToHost, h->stream);
-            if (end && e == hipSuccess) e = hipMemcpyAsync(end, h->c_end + o, c * 8, hipMemcpyDeviceToHost, h->stream);
+            if (key) e = hipMemcpyAsync(key, h->c[0] + o, c * 8, hipMemcpyDeviceToHost, h->stream);
+            if (start && e == hipSuccess) e = hipMemcpyAsync(start, h->c[1] + o, c * 8, hipMemcpyDeviceToHost, h->stream);
+            if (end && e == hipSuccess) e = hipMemcpyAsync(end, h->c[2] + o, c * 8, hipMemcpyDeviceToHost, h->stream);
             if (result && e == hipSuccess)
-                e = hipMemcpyAsync(result, h->c_res + o, c * 8, hipMemcpyDeviceToHost, h->stream);
+                e = hipMemcpyAsync(result, h->c[3] + o, c * 8, hipMemcpyDeviceToHost, h->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
             if (e != hipSuccess) return h->fail(GW_E_DEVICE, "D2H rows: %s", hipGetErrorString(e));
             h->c_head += c;
@@ -4587,10 +4417,10 @@ int gw_rows_device(gw_handle* h, const int64_t** d_key, const int64_t** d_start,
     if (!h) return GW_E_INVALID;
     if (h->fe) {
         const int64_t o = h->c_head;
-        if (d_key) *d_key = h->c_key ? h->c_key + o : nullptr;
-        if (d_start) *d_start = h->c_start ? h->c_start + o : nullptr;
-        if (d_end) *d_end = h->c_end ? h->c_end + o : nullptr;
-        if (d_result) *d_result = h->c_res ? h->c_res + o : nullptr;
+        if (d_key) *d_key = h->c[0] ? h->c[0] + o : nullptr;
+        if (d_start) *d_start = h->c[1] ? h->c[1] + o : nullptr;
+        if (d_end) *d_end = h->c[2] ? h->c[2] + o : nullptr;
+        if (d_result) *d_result = h->c[3] ? h->c[3] + o : nullptr;
         if (n) *n = h->c_rows - h->c_head;
         return GW_OK;
     }
@@ -4602,33 +4432,14 @@ int gw_rows_device(gw_handle* h, const int64_t** d_key, const int64_t** d_start,
             if (rc) return kid_rc(h, kid, rc);
             add += p;
         }
-        if (h->c_rows + add > h->c_cap) {
-            const int64_t cap = std::max<int64_t>(h->c_rows + add, 2 * h->c_cap);
-            int64_t* nb[4] = {nullptr, nullptr, nullptr, nullptr};
-            for (int q = 0; q < 4; ++q) {
-                hipError_t e = hipMalloc((void**)&nb[q], (size_t)cap * 8);
-                if (e != hipSuccess) {
-                    for (int r = 0; r < q; ++r) hipFree(nb[r]);
-                    return h->fail(GW_E_OOM, "composite row buffer: %s", hipGetErrorString(e));
-                }
-            }
-            int64_t* old[4] = {h->c_key, h->c_start, h->c_end, h->c_res};
-            const int64_t live = h->c_rows - h->c_head;
-            for (int q = 0; q < 4; ++q) {
-                if (old[q] && live) hipMemcpyAsync(nb[q], old[q] + h->c_head, live * 8, hipMemcpyDeviceToDevice, h->stream);
-                if (old[q]) { hipStreamSynchronize(h->stream); hipFree(old[q]); }
-            }
-            h->c_key = nb[0]; h->c_start = nb[1]; h->c_end = nb[2]; h->c_res = nb[3];
-            h->c_cap = cap;
-            h->c_rows = live;
-            h->c_head = 0;
-        }
+        const int rrc = reserve_rows(h, h->c_rows + add, 0xf, "composite row buffer");
+        if (rrc) return rrc;
         for (gw_handle* kid : h->kids) {
             const int64_t* k[4];
             int64_t p = 0;
             int rc = gw_rows_device(kid, &k[0], &k[1], &k[2], (const void**)&k[3], &p);
             if (rc) return kid_rc(h, kid, rc);
-            int64_t* dst[4] = {h->c_key, h->c_start, h->c_end, h->c_res};
+            int64_t* dst[4] = {h->c[0], h->c[1], h->c[2], h->c[3]};
             for (int q = 0; q < 4 && p > 0; ++q) {
                 hipError_t e = hipMemcpyAsync(dst[q] + h->c_rows, k[q], p * 8, hipMemcpyDeviceToDevice, h->stream);
                 if (e != hipSuccess) return h->fail(GW_E_DEVICE, "gather rows: %s", hipGetErrorString(e));
@@ -4637,10 +4448,10 @@ int gw_rows_device(gw_handle* h, const int64_t** d_key, const int64_t** d_start,
             if ((rc = gw_clear_rows(kid))) return kid_rc(h, kid, rc);
         }
         const int64_t o = h->c_head;
-        if (d_key) *d_key = h->c_key ? h->c_key + o : nullptr;
-        if (d_start) *d_start = h->c_start ? h->c_start + o : nullptr;
-        if (d_end) *d_end = h->c_end ? h->c_end + o : nullptr;
-        if (d_result) *d_result = h->c_res ? h->c_res + o : nullptr;
+        if (d_key) *d_key = h->c[0] ? h->c[0] + o : nullptr;
+        if (d_start) *d_start = h->c[1] ? h->c[1] + o : nullptr;
+        if (d_end) *d_end = h->c[2] ? h->c[2] + o : nullptr;
+        if (d_result) *d_result = h->c[3] ? h->c[3] + o : nullptr;
         if (n) *n = h->c_rows - h->c_head;
         return GW_OK;
     }
@@ -4973,7 +4784,8 @@ int gw_select_lookup_device(int64_t n, const int64_t* d_sel, int64_t sel_value, 
     *n_out = 0;
     if (n == 0) return GW_OK;
     // scratch per device, grown as needed (every call waits for its launches before returning,
-    // so a later call may free it)
+    // so a later call may free it).  It lives as long as the process: raw pointers, not
+    // DevBufs, whose destructors would call into the HIP runtime during exit
     static std::mutex mu;
     static void* scr[64] = {};
     static size_t cap[64] = {};

@@ -20,6 +20,7 @@
 // inline in its slot of the main table (K1 = 2 / 3 per slot).  A key with more in-flight
 // sessions moves to the wide table (one slot per such key, K2 sessions each, K2 doubled as
 // needed): its runs are replayed there in global memory.  No per-key session limit.
+#include "gw_devmem.h"
 #include "gw_kernels.h"
 #include "gw_session.h"
 #include "gw_sort.h"
@@ -1156,16 +1157,17 @@ struct SessionState {
     hipStream_t stream = nullptr;
     TableView tv{};          // main table (sessions: K1 inline; count windows: the pane ring)
     TableView wv{};          // wide table (sessions of keys with more than K1 in flight)
-    DevStatus* d_st = nullptr;
-    DevStatus* h_st = nullptr;
-    uint32_t* slot[2] = {nullptr, nullptr};  // per record: slot (sort keys, double buffer)
-    uint32_t* perm[2] = {nullptr, nullptr};  // per record: arrival index (sort values)
-    uint32_t* r0 = nullptr;  // punted / retried run heads
-    uint32_t* r1 = nullptr;
-    int64_t* mig = nullptr;  // migration lists (main pass -> wide table)
-    int64_t* rec = nullptr;  // sessions: (ts, value) per record in arrival order
-    int64_t* pu_rec = nullptr;  // sessions: records of keys the prep found no slot for, key | ts | value
-                                // (| gap with per-element gaps)
+    DevBuf<int64_t> tv_mem, wv_mem;  // own tv.base / wv.base
+    DevBuf<DevStatus> d_st;
+    PinnedBuf<DevStatus> h_st;
+    // per-batch buffers of buf_cap records (ensure_bufs)
+    DevBuf<uint32_t> slot[2];  // per record: slot (sort keys, double buffer)
+    DevBuf<uint32_t> perm[2];  // per record: arrival index (sort values)
+    DevBuf<uint32_t> r0, r1;   // punted / retried run heads
+    DevBuf<int64_t> mig;       // migration lists (main pass -> wide table)
+    DevBuf<int64_t> rec;       // sessions: (ts, value) per record in arrival order
+    DevBuf<int64_t> pu_rec;    // sessions: records of keys the prep found no slot for, key | ts | value
+                               // (| gap with per-element gaps)
     bool dyn = false;        // GW_SESSION_DYNAMIC: every record carries its gap (the DYN kernels)
     bool fresh = false;      // h_st matches the device (nothing launched since the last refresh)
     // An ingest whose host follow-up (sort_tail: migrations, the wide pass, records without a
@@ -1176,22 +1178,14 @@ struct SessionState {
     SegArgs sort_a{};
     int64_t sb_wm = 0, sb_new = 0;
     int gshift = 0;          // sessions: the last sort grouped records by slot >> gshift
-    uint32_t* due_list = nullptr;  // fire sweep: main-table slots with something due
-    int64_t due_list_cap = 0;
-    int64_t* cnt_plan = nullptr;  // count windows: long-run plan rows + pane / firing offsets
-    int64_t cnt_plan_cap = 0;
-    int64_t* cnt_tmp = nullptr;   // count windows: pane values of the long runs
-    int64_t cnt_tmp_cap = 0;
-    void* sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
+    DevBuf<uint32_t> due_list;  // fire sweep: main-table slots with something due
+    DevBuf<int64_t> cnt_plan;   // count windows: long-run plan rows + pane / firing offsets
+    DevBuf<int64_t> cnt_tmp;    // count windows: pane values of the long runs
+    DevBuf<char> sort_tmp;
     int64_t buf_cap = 0;
-    int64_t* o_key = nullptr;
-    int64_t* o_start = nullptr;
-    int64_t* o_end = nullptr;
-    int64_t* o_res = nullptr;
-    int64_t o_cap = 0;
-    int64_t* lo_buf[3] = {nullptr, nullptr, nullptr};  // late side output: key | ts | value
-    int64_t lo_cap = 0, lo_head = 0;
+    DevCols<4> o;               // fired rows: key | start | end | result
+    DevCols<3> lo_buf;          // late side output: key | ts | value
+    int64_t lo_head = 0;
     int64_t wm = INT64_MIN;
     gw_stats stats{};
     bool timing = false;
@@ -1292,27 +1286,29 @@ static int begin_launch(SessionState* s, std::string& err) {
 // one-wave kernel (k_status_set, ~1 us) rather than a runtime fill (~5 us and more host time:
 // ~14 per 10M-record sessions step, profiles/r6/configs/kernel_stats_sessions.csv).
 static int zero_word_async(SessionState* s, size_t off, std::string& err) {
-    *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(s->h_st) + off) = 0;
+    *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(s->h_st.p) + off) = 0;
     SCHECK(launch_status_set(s->d_st, (int)(off / 8), 0ull, -1, s->stream));
     return GW_OK;
 }
 
 static int set_word(SessionState* s, size_t off, unsigned long long v, std::string& err) {
-    unsigned long long* hv = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(s->h_st) + off);
+    unsigned long long* hv = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(s->h_st.p) + off);
     *hv = v;
-    SCHECK(hipMemcpyAsync(reinterpret_cast<char*>(s->d_st) + off, hv, 8, hipMemcpyHostToDevice, s->stream));
+    SCHECK(hipMemcpyAsync(reinterpret_cast<char*>(s->d_st.p) + off, hv, 8, hipMemcpyHostToDevice, s->stream));
     SCHECK(hipStreamSynchronize(s->stream));
     return GW_OK;
 }
 
 // ring = sessions (or count panes) per slot, words = int64 words each
-static int alloc_table(SessionState* s, TableView& t, int64_t cap, int ring, int words, std::string& err) {
+static int alloc_table(SessionState* s, TableView& t, DevBuf<int64_t>& mem, int64_t cap, int ring, int words,
+                       std::string& err) {
     t = s->tv;
     t.cap = cap;
     t.ring = ring;
     t.words = words;
     t.stride_w = (int)(((2 + ring * words) + 7) / 8 * 8);
-    SCHECK(hipMalloc((void**)&t.base, table_words(cap, t.stride_w) * 8));  // slots + due times + due summary + keys
+    SCHECK(mem.reserve_discard(table_words(cap, t.stride_w)));  // slots + due times + due summary + keys
+    t.base = mem;
     hipLaunchKernelGGL(k_sess_init, dim3(grid_of(cap + 1)), dim3(256), 0, s->stream, t);
     SCHECK(hipGetLastError());
     return GW_OK;
@@ -1327,8 +1323,8 @@ int session_create(SessionState*& out, const gw_config& cfg, int64_t cap, hipStr
     s->tv.agg = cfg.agg;
     s->wv.agg = cfg.agg;
     std::string& err = why;
-    SCHECK(hipMalloc((void**)&s->d_st, sizeof(DevStatus)));
-    SCHECK(hipHostMalloc((void**)&s->h_st, sizeof(DevStatus), hipHostMallocDefault));
+    SCHECK(s->d_st.reserve_discard(1));
+    SCHECK(s->h_st.alloc(1, hipHostMallocDefault));
     SCHECK(hipMemset(s->d_st, 0, sizeof(DevStatus)));
     memset(s->h_st, 0, sizeof(DevStatus));
     int rc;
@@ -1338,15 +1334,15 @@ int session_create(SessionState*& out, const gw_config& cfg, int64_t cap, hipStr
         int64_t a = size, b = slide;
         while (b) { const int64_t t = a % b; a = b; b = t; }
         s->cg = CountGeom{size, slide, a};
-        rc = alloc_table(s, s->tv, cap, (int)(size / a), cell_words(cfg.agg), why);  // ring of size/g panes
+        rc = alloc_table(s, s->tv, s->tv_mem, cap, (int)(size / a), cell_words(cfg.agg), why);  // ring of size/g panes
         if (rc) { session_destroy(s); return rc; }
         out = s;
         return GW_OK;
     }
     // K1 so that the slot is one 64-byte line: 2 sessions (sum/count/min/max), 1 (avg)
     const int words = cell_words(cfg.agg) == 2 ? 4 : 3;
-    rc = alloc_table(s, s->tv, cap, words == 3 ? 2 : 1, words, why);
-    if (rc == GW_OK) rc = alloc_table(s, s->wv, 1024, 4, kWideWords, why);
+    rc = alloc_table(s, s->tv, s->tv_mem, cap, words == 3 ? 2 : 1, words, why);
+    if (rc == GW_OK) rc = alloc_table(s, s->wv, s->wv_mem, 1024, 4, kWideWords, why);
     if (rc) { session_destroy(s); return rc; }
     out = s;
     return GW_OK;
@@ -1355,16 +1351,6 @@ int session_create(SessionState*& out, const gw_config& cfg, int64_t cap, hipStr
 void session_destroy(SessionState* s) {
     if (!s) return;
     hipStreamSynchronize(s->stream);
-    hipFree(s->tv.base);
-    hipFree(s->wv.base);
-    hipFree(s->d_st);
-    hipHostFree(s->h_st);
-    for (int q = 0; q < 2; ++q) { hipFree(s->slot[q]); hipFree(s->perm[q]); }
-    hipFree(s->r0); hipFree(s->r1); hipFree(s->mig); hipFree(s->rec); hipFree(s->pu_rec);
-    hipFree(s->cnt_plan); hipFree(s->cnt_tmp); hipFree(s->due_list);
-    hipFree(s->sort_tmp);
-    hipFree(s->o_key); hipFree(s->o_start); hipFree(s->o_end); hipFree(s->o_res);
-    for (auto* p : s->lo_buf) hipFree(p);
     for (int w = 0; w < kTimers; ++w) for (auto& p : s->ev_pending[w]) s->ev_pool.push_back(p);
     for (auto& p : s->ev_pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     delete s;
@@ -1374,23 +1360,14 @@ static int ensure_bufs(SessionState* s, int64_t n, std::string& err) {
     if (n <= s->buf_cap) return GW_OK;
     const int64_t c = std::max<int64_t>(n + n / 4, 1 << 16);
     SCHECK(hipStreamSynchronize(s->stream));
-    for (int q = 0; q < 2; ++q) { hipFree(s->slot[q]); hipFree(s->perm[q]); }
-    hipFree(s->r0); hipFree(s->r1); hipFree(s->mig); hipFree(s->sort_tmp); hipFree(s->rec); hipFree(s->pu_rec);
-    s->mig = nullptr;
-    s->rec = nullptr;
-    s->pu_rec = nullptr;
-    for (int q = 0; q < 2; ++q) {
-        SCHECK(hipMalloc((void**)&s->slot[q], c * 4));
-        SCHECK(hipMalloc((void**)&s->perm[q], c * 4));
+    s->buf_cap = 0;  // a failure below leaves some buffers empty: the next call starts over
+    for (auto* b : {&s->slot[0], &s->slot[1], &s->perm[0], &s->perm[1], &s->r0, &s->r1}) SCHECK(b->reserve_discard(c));
+    if (!s->count_mode) {
+        SCHECK(s->mig.reserve_discard(c * (2 + kWideWords * kLaneSess)));
+        SCHECK(s->rec.reserve_discard(c * (s->dyn ? 4 : 2)));
+        SCHECK(s->pu_rec.reserve_discard(c * (s->dyn ? 4 : 3)));
     }
-    SCHECK(hipMalloc((void**)&s->r0, c * 4));
-    SCHECK(hipMalloc((void**)&s->r1, c * 4));
-    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->mig, (size_t)c * (2 + kWideWords * kLaneSess) * 8));
-    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->rec, (size_t)c * (s->dyn ? 32 : 16)));
-    if (!s->count_mode) SCHECK(hipMalloc((void**)&s->pu_rec, (size_t)c * (s->dyn ? 32 : 24)));
-    const size_t bytes = (size_t)sort_scratch_bytes(c);
-    SCHECK(hipMalloc(&s->sort_tmp, bytes));
-    s->sort_tmp_bytes = bytes;
+    SCHECK(s->sort_tmp.reserve_discard((int64_t)sort_scratch_bytes(c)));
     s->buf_cap = c;
     return GW_OK;
 }
@@ -1423,7 +1400,8 @@ static int sort_by_slot(SessionState* s, int64_t n, int64_t cap, const uint32_t*
 // Grow a table to new_cap slots (and/or new ring): rehash its state into a fresh table.
 static int regrow(SessionState* s, TableView& t, int64_t new_cap, int new_ring, bool wide, std::string& err) {
     TableView nt;
-    int rc = alloc_table(s, nt, new_cap, new_ring, t.words, err);
+    DevBuf<int64_t> nmem;
+    int rc = alloc_table(s, nt, nmem, new_cap, new_ring, t.words, err);
     if (rc) return rc;
     if (wide) {
         SCHECK(launch_status_set(s->d_st, offsetof(DevStatus, pad[2]) / 8, 0, -1, s->stream));
@@ -1435,7 +1413,7 @@ static int regrow(SessionState* s, TableView& t, int64_t new_cap, int new_ring, 
                        wide ? -1 : 1);
     SCHECK(hipGetLastError());
     SCHECK(hipStreamSynchronize(s->stream));
-    hipFree(t.base);
+    (wide ? s->wv_mem : s->tv_mem) = std::move(nmem);
     t = nt;
     s->stats.rehashes++;
     rc = session_refresh(s, err);
@@ -1456,35 +1434,18 @@ static int ensure_wide(SessionState* s, int64_t add, int64_t need, std::string& 
 }
 
 static int ensure_rows(SessionState* s, int64_t need, std::string& err) {
-    if (need <= s->o_cap) return GW_OK;
+    if (need <= s->o.cap) return GW_OK;
     const int64_t before = (int64_t)s->h_st->rows;
     const int64_t c = std::max<int64_t>(need + need / 4, 1 << 16);
-    int64_t* nb[4];
-    for (int q = 0; q < 4; ++q) SCHECK(hipMalloc((void**)&nb[q], c * 8));
-    int64_t* old[4] = {s->o_key, s->o_start, s->o_end, s->o_res};
-    for (int q = 0; q < 4; ++q) {
-        if (old[q] && before) SCHECK(hipMemcpyAsync(nb[q], old[q], before * 8, hipMemcpyDeviceToDevice, s->stream));
-    }
-    SCHECK(hipStreamSynchronize(s->stream));
-    for (int q = 0; q < 4; ++q) hipFree(old[q]);
-    s->o_key = nb[0]; s->o_start = nb[1]; s->o_end = nb[2]; s->o_res = nb[3];
-    s->o_cap = c;
+    SCHECK(s->o.reserve_keep(c, 0, before, s->stream));
     return GW_OK;
 }
 
 static int ensure_late(SessionState* s, int64_t need, std::string& err) {
-    if (need <= s->lo_cap) return GW_OK;
+    if (need <= s->lo_buf.cap) return GW_OK;
     const int64_t used = (int64_t)s->h_st->n_late_out;  // exact: the session path is synchronous
     const int64_t c = std::max<int64_t>(need + need / 2, 1 << 16);
-    for (int q = 0; q < 3; ++q) {
-        int64_t* nb;
-        SCHECK(hipMalloc((void**)&nb, c * 8));
-        if (s->lo_buf[q] && used) SCHECK(hipMemcpyAsync(nb, s->lo_buf[q], used * 8, hipMemcpyDeviceToDevice, s->stream));
-        SCHECK(hipStreamSynchronize(s->stream));
-        hipFree(s->lo_buf[q]);
-        s->lo_buf[q] = nb;
-    }
-    s->lo_cap = c;
+    SCHECK(s->lo_buf.reserve_keep(c, 0, used, s->stream));
     return GW_OK;
 }
 
@@ -1558,7 +1519,7 @@ static int launch_count_apply(SessionState* s, const uint32_t* ks, const uint32_
     const int64_t* v = s->cfg.agg == GW_COUNT ? nullptr : val;
 #define L(A)                                                                                               \
     hipLaunchKernelGGL(k_cnt_apply<A>, dim3(grid_of(n)), dim3(256), 0, s->stream, s->tv, s->cg, ks, perm, n, v, \
-                       s->o_key, s->o_start, s->o_end, s->o_res, s->r0, s->d_st)
+                       s->o[0], s->o[1], s->o[2], s->o[3], s->r0, s->d_st)
     GW_AGG_SWITCH(s->cfg.agg, L);
 #undef L
     SCHECK(hipGetLastError());
@@ -1568,11 +1529,9 @@ static int launch_count_apply(SessionState* s, const uint32_t* ks, const uint32_
     // plan rows of the long runs, their pane / firing offsets (device scan), then the three
     // launches over upper bounds of the pane and firing counts (no host round trip)
     const int64_t pw = nl * kPlanWords + 2 * (nl + 1);
-    if (pw > s->cnt_plan_cap) {
+    if (pw > s->cnt_plan.cap) {
         SCHECK(hipStreamSynchronize(s->stream));
-        hipFree(s->cnt_plan);
-        s->cnt_plan_cap = std::max<int64_t>(pw * 2, 4096);
-        SCHECK(hipMalloc((void**)&s->cnt_plan, s->cnt_plan_cap * 8));
+        SCHECK(s->cnt_plan.reserve_discard(std::max<int64_t>(pw * 2, 4096)));
     }
     const CountGeom& G = s->cg;
     int64_t* dpo = s->cnt_plan + nl * kPlanWords;
@@ -1582,11 +1541,9 @@ static int launch_count_apply(SessionState* s, const uint32_t* ks, const uint32_
     hipLaunchKernelGGL(k_cnt_plan_scan, dim3(1), dim3(1024), 0, s->stream, dpo, dfo, nl);
     const int64_t np_max = n / G.g + 2 * nl, nf_max = n / G.slide + nl;
     const int W = s->tv.words;
-    if (np_max * W > s->cnt_tmp_cap) {
+    if (np_max * W > s->cnt_tmp.cap) {
         SCHECK(hipStreamSynchronize(s->stream));
-        hipFree(s->cnt_tmp);
-        s->cnt_tmp_cap = std::max<int64_t>(np_max * W + np_max * W / 2, 1 << 16);
-        SCHECK(hipMalloc((void**)&s->cnt_tmp, s->cnt_tmp_cap * 8));
+        SCHECK(s->cnt_tmp.reserve_discard(std::max<int64_t>(np_max * W + np_max * W / 2, 1 << 16)));
     }
     const bool wave = G.g >= 16;
     const unsigned pg = (unsigned)((np_max * (wave ? 64 : 1) + 255) / 256);
@@ -1599,7 +1556,7 @@ static int launch_count_apply(SessionState* s, const uint32_t* ks, const uint32_
                            s->cnt_plan, dpo, nl, s->cnt_tmp);                                                  \
     if (nf_max > 0)                                                                                            \
         hipLaunchKernelGGL(k_cnt_fires<A>, dim3((unsigned)((nf_max + 255) / 256)), dim3(256), 0, s->stream, s->tv, G, \
-                           s->cnt_plan, dpo, dfo, nl, s->cnt_tmp, s->o_key, s->o_start, s->o_end, s->o_res, s->d_st)
+                           s->cnt_plan, dpo, dfo, nl, s->cnt_tmp, s->o[0], s->o[1], s->o[2], s->o[3], s->d_st)
     GW_AGG_SWITCH(s->cfg.agg, L);
 #undef L
     hipLaunchKernelGGL(k_cnt_ring, dim3((unsigned)((nl * s->tv.ring + 255) / 256)), dim3(256), 0, s->stream, s->tv, G,
@@ -1643,7 +1600,7 @@ static int seg_common(SessionState* s, SegArgs& a, int64_t n, int64_t wm, std::s
     a.st = s->d_st;
     if (a.lateness > 0) {  // an element fires at most one window at once
         if ((rc = ensure_rows(s, (int64_t)s->h_st->rows + n, err))) return rc;
-        a.o_key = s->o_key; a.o_start = s->o_start; a.o_end = s->o_end; a.o_res = s->o_res;
+        a.o_key = s->o[0]; a.o_start = s->o[1]; a.o_end = s->o[2]; a.o_res = s->o[3];
     }
     if (s->cfg.flags & GW_FLAG_LATE_SIDE_OUTPUT) {
         if ((rc = ensure_late(s, (int64_t)s->h_st->n_late_out + n, err))) return rc;
@@ -1831,12 +1788,9 @@ int session_fire(SessionState* s, int64_t wm, int64_t* fired, std::string& err) 
         auto ev = s->timing ? get_ev(s) : std::pair<hipEvent_t, hipEvent_t>{};
         if (s->timing) SCHECK(hipEventRecord(ev.first, s->stream));
         const unsigned fg = (unsigned)std::min<int64_t>(1024, std::max<int64_t>(1, (s->tv.cap + 1 + 255) / 256));
-        if (s->due_list_cap < s->tv.cap + 1) {
+        if (s->due_list.cap < s->tv.cap + 1) {
             SCHECK(hipStreamSynchronize(s->stream));
-            hipFree(s->due_list);
-            s->due_list = nullptr;
-            SCHECK(hipMalloc((void**)&s->due_list, (size_t)(s->tv.cap + 1) * 4));
-            s->due_list_cap = s->tv.cap + 1;
+            SCHECK(s->due_list.reserve_discard(s->tv.cap + 1));
         }
         if ((rc = zero_word_async(s, offsetof(DevStatus, n_refire), err))) return rc;  // due-list cursor
         const unsigned sg = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, (s->tv.cap + 1) / 2048));
@@ -1844,10 +1798,10 @@ int session_fire(SessionState* s, int64_t wm, int64_t* fired, std::string& err) 
         const int purge = (int)(s->cfg.allowed_lateness > 0 && s->cfg.trigger == GW_PURGING_EVENT_TIME_TRIGGER);
 #define L(A)                                                                                               \
         hipLaunchKernelGGL(k_sess_fire<A>, dim3(fg), dim3(256), 0, s->stream, s->tv, s->due_list, wm,        \
-                           s->cfg.allowed_lateness, purge, s->o_key, s->o_start, s->o_end, s->o_res, s->d_st); \
+                           s->cfg.allowed_lateness, purge, s->o[0], s->o[1], s->o[2], s->o[3], s->d_st); \
         if (s->h_st->pad[2])                                                                                \
         hipLaunchKernelGGL(k_sess_fire_wide<A>, dim3(grid_of(s->wv.cap + 1)), dim3(256), 0, s->stream, s->wv, wm, \
-                           s->cfg.allowed_lateness, purge, s->o_key, s->o_start, s->o_end, s->o_res, s->d_st)
+                           s->cfg.allowed_lateness, purge, s->o[0], s->o[1], s->o[2], s->o[3], s->d_st)
         GW_AGG_SWITCH(s->cfg.agg, L);
 #undef L
         SCHECK(hipGetLastError());
@@ -1869,7 +1823,7 @@ int session_fire(SessionState* s, int64_t wm, int64_t* fired, std::string& err) 
 }
 
 void session_rows(SessionState* s, int64_t** k, int64_t** st, int64_t** en, int64_t** r, int64_t* total) {
-    *k = s->o_key; *st = s->o_start; *en = s->o_end; *r = s->o_res;
+    *k = s->o[0]; *st = s->o[1]; *en = s->o[2]; *r = s->o[3];
     *total = (int64_t)s->h_st->rows;
 }
 
@@ -1931,14 +1885,13 @@ static int count_restore(SessionState* s, const int64_t* ent, int64_t n, std::st
         if ((rc = regrow(s, s->tv, want, s->tv.ring, false, err))) return rc;
     }
     const int64_t bytes = n * session_entry_words(s) * 8;
-    int64_t* d = nullptr;
-    SCHECK(hipMalloc((void**)&d, bytes));
+    DevBuf<char> d;
+    SCHECK(d.reserve_discard(bytes));
     SCHECK(hipMemcpy(d, ent, bytes, hipMemcpyHostToDevice));
     if ((rc = set_word(s, offsetof(DevStatus, overflow), 0, err))) return rc;
-    hipLaunchKernelGGL(k_cnt_restore, dim3(grid_of(n)), dim3(256), 0, s->stream, s->tv, d, n, s->d_st);
+    hipLaunchKernelGGL(k_cnt_restore, dim3(grid_of(n)), dim3(256), 0, s->stream, s->tv, (const int64_t*)d.p, n, s->d_st);
     SCHECK(hipGetLastError());
     rc = session_refresh(s, err);
-    hipFree(d);
     if (rc) return rc;
     if (s->h_st->flags & GW_DF_TABLE_FULL) { err = "count-window state table overflow"; return GW_E_OOM; }
     if (s->h_st->overflow) {
@@ -1983,10 +1936,10 @@ int session_restore(SessionState* s, const int64_t* ent, int64_t n, std::string&
         while ((double)(s->h_st->used_slots + nk) > 0.7 * (double)want) want *= 2;
         if ((rc = regrow(s, s->tv, want, s->tv.ring, false, err))) return rc;
     }
-    int64_t *d_k = nullptr, *d_o = nullptr, *d_s = nullptr;
-    SCHECK(hipMalloc((void**)&d_k, nk * 8));
-    SCHECK(hipMalloc((void**)&d_o, (nk + 1) * 8));
-    SCHECK(hipMalloc((void**)&d_s, n * 40));
+    DevBuf<int64_t> d_k, d_o, d_s;
+    SCHECK(d_k.reserve_discard(nk));
+    SCHECK(d_o.reserve_discard(nk + 1));
+    SCHECK(d_s.reserve_discard(n * 5));
     SCHECK(hipMemcpy(d_k, rk.data(), nk * 8, hipMemcpyHostToDevice));
     SCHECK(hipMemcpy(d_o, roff.data(), (nk + 1) * 8, hipMemcpyHostToDevice));
     SCHECK(hipMemcpy(d_s, rs.data(), n * 40, hipMemcpyHostToDevice));
@@ -1995,9 +1948,6 @@ int session_restore(SessionState* s, const int64_t* ent, int64_t n, std::string&
                        s->cfg.allowed_lateness, s->d_st);
     SCHECK(hipGetLastError());
     rc = session_refresh(s, err);
-    hipFree(d_k);
-    hipFree(d_o);
-    hipFree(d_s);
     if (rc) return rc;
     if (s->h_st->flags & GW_DF_TABLE_FULL) { err = "session state table full"; return GW_E_OOM; }
     if (s->h_st->overflow) {
