@@ -62,6 +62,8 @@ EXPORTS = [
     "gw_exchange_enable_packing", "gw_exchange_last_packed", "gw_exchange_plan_packed",
     "gw_exchange_set_unpack", "gw_exchange_last_words", "gw_ingest_packed_device",
     "gw_ingest_gap", "gw_ingest_gap_device",
+    "gw_row_encoded_bytes", "gw_encode_rows_device", "gw_encode_rows_host", "gw_drain_serialized",
+    "gw_rows_serialized_device",
 ]
 EXCHANGE_ID_BYTES = 128
 EXCHANGE_RECV_SETS = 3  # gpuwin.h GW_EXCHANGE_RECV_SETS
@@ -82,6 +84,32 @@ def record_layout(types: str, key_field: int, value_field: int = -1) -> GwRecord
     """types: JVM type codes of the Tuple fields, e.g. "JJ" for Tuple2<Long, Long>."""
     lay = GwRecordLayout()
     lay.nfields, lay.key_field, lay.value_field = len(types), key_field, value_field
+    lay.types = types.encode()
+    return lay
+
+
+# gpuwin.h GW_ROW_*: where a field of an emitted row comes from; GW_ENCODE_*
+GW_ROW_KEY, GW_ROW_START, GW_ROW_END, GW_ROW_RESULT, GW_ROW_PAYLOAD = 0, 1, 2, 3, 4
+ENCODE_GLOBAL_WINDOW = 1
+ENCODE_MAX_CHANNELS = 128
+NO_WATERMARK = -(1 << 63)  # INT64_MIN: no Watermark element behind the rows
+
+
+class GwRowLayout(ctypes.Structure):
+    """gw_row_layout: the Tuple a fired row is emitted as (gw_encode_rows_*, gw_drain_serialized)."""
+    _fields_ = [("nfields", ctypes.c_int32), ("source", ctypes.c_int32 * 8), ("types", ctypes.c_char * 8)]
+
+
+def row_layout(types: str, sources) -> GwRowLayout:
+    """types: JVM type codes of the emitted fields ('J', 'D', 'I'); sources: GW_ROW_* per field,
+    e.g. row_layout("JJ", (GW_ROW_KEY, GW_ROW_RESULT)) for Tuple2<Long, Long>(key, result)."""
+    sources = list(sources)
+    if len(sources) != len(types) or len(types) > 8:
+        raise ValueError("one source per field, at most 8 fields")
+    lay = GwRowLayout()
+    lay.nfields = len(types)
+    for i, s in enumerate(sources):
+        lay.source[i] = int(s)
     lay.types = types.encode()
     return lay
 
@@ -233,6 +261,13 @@ def lib() -> ctypes.CDLL:
         "gw_exchange_set_unpack": (c_int, [p, i32]),
         "gw_exchange_last_words": (c_int, [p, P64, ctypes.POINTER(p), ctypes.POINTER(GwPackGeom)]),
         "gw_ingest_packed_device": (c_int, [p, i64, p, p, p, i64, p, ctypes.POINTER(GwPackGeom), p]),
+        "gw_row_encoded_bytes": (i64, [ctypes.POINTER(GwRowLayout)]),
+        "gw_encode_rows_device": (c_int, [i64, p, p, p, p, p, ctypes.POINTER(GwRowLayout), i32, i32, i32, i64, p, i64,
+                                          p, p, p]),
+        "gw_encode_rows_host": (c_int, [i64, p, p, p, p, p, ctypes.POINTER(GwRowLayout), i32, i32, i32, i64, p, i64,
+                                        p, p]),
+        "gw_drain_serialized": (c_int, [p, ctypes.POINTER(GwRowLayout), i32, i32, i64, p, i64, p, p, P64]),
+        "gw_rows_serialized_device": (c_int, [p, ctypes.POINTER(GwRowLayout), i32, i32, i64, p, i64, p, p, P64, p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -347,3 +382,24 @@ def unpack_records(words, g: GwPackGeom, with_values: bool = True):
     check(lib().gw_unpack_records(n, words.ctypes.data, ctypes.byref(g), k.ctypes.data, t.ctypes.data,
                                   None if v is None else v.ctypes.data))
     return k, t, v
+
+
+def encode_rows_host(key, start, end, result, layout: GwRowLayout, payload=None, mode: int = 0, channels: int = 1,
+                     max_parallelism: int = 128, watermark=None, cap=None):
+    """gw_encode_rows_host: the rows as serialized stream elements, one bytes object per channel."""
+    import numpy as np
+    cols = [np.ascontiguousarray(c).view(np.int64) for c in (key, start, end, result)]
+    pay = None if payload is None else np.ascontiguousarray(payload, np.int64)
+    n = cols[0].size
+    if cap is None:
+        rb = lib().gw_row_encoded_bytes(ctypes.byref(layout))
+        if rb < 0:
+            check(int(rb))
+        cap = n * rb + channels * 32
+    buf = np.empty(max(cap, 1), np.uint8)
+    off, nb = np.zeros(channels, np.int64), np.zeros(channels, np.int64)
+    check(lib().gw_encode_rows_host(n, *[c.ctypes.data for c in cols], None if pay is None else pay.ctypes.data,
+                                    ctypes.byref(layout), mode, channels, max_parallelism,
+                                    NO_WATERMARK if watermark is None else int(watermark), buf.ctypes.data, cap,
+                                    off.ctypes.data, nb.ctypes.data))
+    return [buf[o:o + b].tobytes() for o, b in zip(off.tolist(), nb.tolist())]

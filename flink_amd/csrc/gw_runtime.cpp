@@ -28,6 +28,7 @@
 #include "gw_first.h"
 #include "gw_kernels.h"
 #include "gw_netbuf.h"
+#include "gw_rowenc.h"
 #include "gw_session.h"
 #include "gw_snapshot.h"
 #include "gw_sort.h"
@@ -193,6 +194,7 @@ struct gw_handle {
     int64_t cls_J = 0, cls_j = 0, cls_slide = 0, cls_off = 0;  // a child's class
     DevCols<5> c;  // key | start | end | result | payload (first-element handles only)
     int64_t c_rows = 0, c_head = 0;
+    DevBuf<uint8_t> ser_bytes;  // gw_drain_serialized: the encoded rows before their copy to the host
     // First-element handle (GW_FLAG_FIRST_ELEMENT, gw_first.hip): kids[0] folds the aggregate,
     // kids[1] the MIN of each record's arrival sequence; the payload log keeps every record's
     // payload (a ring indexed by sequence) until all windows that could hold it are cleaned.
@@ -4950,6 +4952,161 @@ int gw_partition_device(int64_t n, const int64_t* d_key, const int32_t* d_key_ha
     hipError_t e = launch_partition(n, d_key, d_key_hash, d_ts, (const int64_t*)d_value, max_p, p, d_key_out,
                                     d_ts_out, (int64_t*)d_value_out, d_counts, d_scratch, s);
     if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return GW_E_DEVICE; }
+    return GW_OK;
+}
+
+// ---- network-buffer output (gw_rowenc.hip) -------------------------------------------------
+static int row_encode_args(int64_t n, const gw_row_layout* l, int32_t mode, bool have_payload, int32_t channels,
+                           int32_t max_p, int64_t cap, const int64_t* chan_off, const int64_t* chan_bytes, RowPlan& p,
+                           std::string& why) {
+    if (n < 0 || cap < 0 || !chan_off || !chan_bytes || channels < 1) { why = "row encode: bad argument"; return GW_E_INVALID; }
+    const int rc = row_plan(l, mode, have_payload, p, why);
+    if (rc) return rc;
+    if (channels > kEncMaxChannels) { why = "row encode: more than 128 channels"; return GW_E_UNSUPPORTED; }
+    if (channels > 1 && (max_p < channels || max_p > 32768)) {
+        why = "row encode: max parallelism outside [channels, 32768]";
+        return GW_E_INVALID;
+    }
+    return GW_OK;
+}
+
+int64_t gw_row_encoded_bytes(const gw_row_layout* l) {
+    RowPlan p;
+    std::string why;
+    // (whether a payload column exists is the call's business, not the layout's)
+    const int rc = row_plan(l, 0, true, p, why);
+    if (rc) { g_create_error = why; return rc; }
+    return p.row_bytes;
+}
+
+int gw_encode_rows_host(int64_t n, const int64_t* key, const int64_t* start, const int64_t* end, const void* result,
+                        const int64_t* payload, const gw_row_layout* l, int32_t mode, int32_t channels, int32_t max_p,
+                        int64_t watermark, void* bytes, int64_t cap, int64_t* chan_off, int64_t* chan_bytes) {
+    RowPlan p;
+    std::string why;
+    int rc = row_encode_args(n, l, mode, payload != nullptr, channels, max_p, cap, chan_off, chan_bytes, p, why);
+    if (rc == GW_OK && ((n > 0 && (!key || !start || !end || !result)) || (cap > 0 && !bytes))) {
+        why = "row encode: null column or buffer";
+        rc = GW_E_INVALID;
+    }
+    if (rc == GW_OK) {
+        const int64_t* col[kRowSources] = {key, start, end, (const int64_t*)result, payload};
+        try {
+            rc = row_encode_host(n, col, p, channels, max_p, watermark, (uint8_t*)bytes, cap, chan_off, chan_bytes, why);
+        } catch (const std::bad_alloc&) {
+            why = "row encode: out of host memory";
+            rc = GW_E_OOM;
+        }
+    }
+    if (rc) g_create_error = why;
+    return rc;
+}
+
+static int encode_rows_device(int64_t n, const int64_t* const col[kRowSources], const gw_row_layout* l, int32_t mode,
+                              int32_t channels, int32_t max_p, int64_t watermark, void* d_bytes, int64_t cap,
+                              int64_t* chan_off, int64_t* chan_bytes, hipStream_t s, std::string& why) {
+    RowPlan p;
+    int rc = row_encode_args(n, l, mode, col[GW_ROW_PAYLOAD] != nullptr, channels, max_p, cap, chan_off, chan_bytes, p, why);
+    if (rc) return rc;
+    if ((n > 0 && (!col[GW_ROW_KEY] || !col[GW_ROW_START] || !col[GW_ROW_END] || !col[GW_ROW_RESULT])) ||
+        (cap > 0 && !d_bytes) || ((uintptr_t)d_bytes & 15)) {
+        why = "row encode: null column, or a byte buffer that is null or not 16-byte aligned";
+        return GW_E_INVALID;
+    }
+    try {
+        return row_encode_run(n, col, p, channels, max_p, watermark, (uint8_t*)d_bytes, cap, chan_off, chan_bytes, s, why);
+    } catch (const std::bad_alloc&) {
+        why = "row encode: out of host memory";
+        return GW_E_OOM;
+    }
+}
+
+int gw_encode_rows_device(int64_t n, const int64_t* d_key, const int64_t* d_start, const int64_t* d_end,
+                          const void* d_result, const int64_t* d_payload, const gw_row_layout* l, int32_t mode,
+                          int32_t channels, int32_t max_p, int64_t watermark, void* d_bytes, int64_t cap,
+                          int64_t* chan_off, int64_t* chan_bytes, void* stream) {
+    const int64_t* col[kRowSources] = {d_key, d_start, d_end, (const int64_t*)d_result, d_payload};
+    std::string why;
+    const int rc = encode_rows_device(n, col, l, mode, channels, max_p, watermark, d_bytes, cap, chan_off, chan_bytes,
+                                      (hipStream_t)stream, why);
+    if (rc) g_create_error = why;
+    return rc;
+}
+
+// A handle (or a child of it) was fed a key_hash column: its keys are caller ids.
+static bool key_hash_fed(const gw_handle* h) {
+    if (h->khm.cap) return true;
+    for (const gw_handle* kid : h->kids)
+        if (key_hash_fed(kid)) return true;
+    return false;
+}
+
+// The pending rows of h encoded into d_bytes (device) on the handle's stream.
+static int rows_serialized(gw_handle* h, const char* what, const gw_row_layout* l, int32_t channels, int32_t max_p,
+                           int64_t watermark, void* d_bytes, int64_t cap, int64_t* chan_off, int64_t* chan_bytes,
+                           int64_t* n_rows) {
+    if (channels > 1 && key_hash_fed(h))
+        return h->fail(GW_E_UNSUPPORTED, "%s: the handle was fed key hashes, which its rows do not carry: the channel "
+                                         "of such a key cannot be derived (channels = 1 only)", what);
+    const int64_t* col[kRowSources] = {};
+    int64_t pending = 0;
+    int rc = gw_rows_device(h, &col[0], &col[1], &col[2], (const void**)&col[3], &pending);
+    if (rc) return rc;
+    if (h->fe && h->c[4]) col[GW_ROW_PAYLOAD] = h->c[4] + h->c_head;
+    const bool count_windows = h->cfg.assigner == GW_COUNT_TUMBLING || h->cfg.assigner == GW_COUNT_SLIDING;
+    std::string why;
+    rc = encode_rows_device(pending, col, l, count_windows ? GW_ENCODE_GLOBAL_WINDOW : 0, channels, max_p, watermark,
+                            d_bytes, cap, chan_off, chan_bytes, h->stream, why);
+    if (rc) {  // (not h->fail: a row that does not fit its 'I' field does not fail the operator)
+        h->err = std::string(what) + ": " + why;
+        return rc;
+    }
+    if (n_rows) *n_rows = pending;
+    return GW_OK;
+}
+
+int gw_rows_serialized_device(gw_handle* h, const gw_row_layout* l, int32_t channels, int32_t max_p, int64_t watermark,
+                              void* d_bytes, int64_t cap, int64_t* chan_off, int64_t* chan_bytes, int64_t* n_rows,
+                              void* stream) {
+    if (!h) return GW_E_INVALID;
+    if (h->failed) return GW_E_STATE;
+    hipSetDevice(h->cfg.device);
+    if (n_rows) *n_rows = 0;
+    // the consumer's stream may still use d_bytes: write them behind its pending work (the call
+    // returns with the bytes complete, so the consumer needs no ordering of its own)
+    hipStream_t cs = (hipStream_t)stream;
+    if (cs != h->stream) {
+        hipEventRecord(h->ev_in, cs);
+        hipStreamWaitEvent(h->stream, h->ev_in, 0);
+    }
+    return rows_serialized(h, "gw_rows_serialized_device", l, channels, max_p, watermark, d_bytes, cap, chan_off,
+                           chan_bytes, n_rows);
+}
+
+int gw_drain_serialized(gw_handle* h, const gw_row_layout* l, int32_t channels, int32_t max_p, int64_t watermark,
+                        void* bytes, int64_t cap, int64_t* chan_off, int64_t* chan_bytes, int64_t* n_rows) {
+    if (!h) return GW_E_INVALID;
+    if (h->failed) return GW_E_STATE;
+    if (cap < 0 || (cap > 0 && !bytes)) return h->fail(GW_E_INVALID, "gw_drain_serialized: bad byte buffer");
+    hipSetDevice(h->cfg.device);
+    if (n_rows) *n_rows = 0;
+    if (h->ser_bytes.reserve_discard(std::max<int64_t>(cap, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return h->fail(GW_E_OOM, "gw_drain_serialized: staging of %lld bytes", (long long)cap);
+    }
+    int64_t rows = 0;
+    int rc = rows_serialized(h, "gw_drain_serialized", l, channels, max_p, watermark, h->ser_bytes.get(), cap, chan_off,
+                             chan_bytes, &rows);
+    if (rc) return rc;
+    const int64_t used = chan_off[channels - 1] + chan_bytes[channels - 1];
+    if (used > 0) {
+        hipError_t e = hipMemcpyAsync(bytes, h->ser_bytes.get(), (size_t)used, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return h->fail(GW_E_DEVICE, "D2H serialized rows: %s", hipGetErrorString(e));
+    }
+    if (h->fe) h->c_head = h->c_rows = 0;  // as gw_drain_payload leaves them
+    else if ((rc = gw_clear_rows(h))) return rc;
+    if (n_rows) *n_rows = rows;
     return GW_OK;
 }
 

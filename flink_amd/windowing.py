@@ -885,6 +885,58 @@ class GpuWindowOperator:
         N.check(rc, self._h)
         return [x.value for x in p], n.value
 
+    # network-buffer output ------------------------------------------------------------
+    def _serialized_cap(self, layout, channels: int) -> int:
+        rb = N.lib().gw_row_encoded_bytes(ctypes.byref(layout))
+        if rb < 0:
+            N.check(int(rb))
+        return self.pending_rows() * rb + channels * 32  # a watermark and alignment padding per channel
+
+    def _no_rows_serialized(self, layout, channels, max_parallelism, watermark):
+        z = np.empty(0, np.int64)
+        return N.encode_rows_host(z, z, z, z, layout, payload=z if self._payload else None, channels=channels,
+                                  max_parallelism=max_parallelism, watermark=watermark)
+
+    def drain_serialized(self, layout: "N.GwRowLayout", channels: int = 1, max_parallelism: int = 128,
+                         watermark: Optional[int] = None) -> list:
+        """All pending rows as the serialized stream elements a Flink task would have written for
+        them (gw_drain_serialized; netbuf.record per row, timestamp = window end - 1), encoded on
+        the GPU: one bytes object per downstream channel (channels > 1: keyBy on the row key),
+        each ending with Watermark(watermark) when one is given.  The rows are removed."""
+        if self._deferred:  # staggered and no element yet: no rows
+            return self._no_rows_serialized(layout, channels, max_parallelism, watermark)
+        cap = self._serialized_cap(layout, channels)
+        buf = np.empty(max(cap, 1), np.uint8)
+        off, nb = np.zeros(channels, np.int64), np.zeros(channels, np.int64)
+        N.check(N.lib().gw_drain_serialized(self._h, ctypes.byref(layout), channels, max_parallelism,
+                                            N.NO_WATERMARK if watermark is None else int(watermark), _ptr(buf), cap,
+                                            _ptr(off), _ptr(nb), None), self._h)
+        return [buf[o:o + b].tobytes() for o, b in zip(off.tolist(), nb.tolist())]
+
+    def rows_serialized_device(self, layout: "N.GwRowLayout", channels: int = 1, max_parallelism: int = 128,
+                               watermark: Optional[int] = None, stream=None):
+        """Same, into device memory (gw_rows_serialized_device): (bytes, ranges) with bytes a
+        torch.uint8 tensor on the operator's device and ranges a list of (offset, length) per
+        channel, e.g. for another operator's process_serialized_device(bytes[o:o + n], ...).  The
+        rows stay pending: follow with clear_rows()."""
+        import torch
+        dev = f"cuda:{self.cfg.device}"
+        if self._deferred:
+            parts = self._no_rows_serialized(layout, channels, max_parallelism, watermark)
+            data = np.frombuffer(b"".join(parts), np.uint8).copy()
+            ends = np.cumsum([len(x) for x in parts]).tolist()
+            return torch.from_numpy(data).to(dev), [(e - len(x), len(x)) for e, x in zip(ends, parts)]
+        cap = self._serialized_cap(layout, channels)
+        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        off, nb = np.zeros(channels, np.int64), np.zeros(channels, np.int64)
+        N.check(N.lib().gw_rows_serialized_device(self._h, ctypes.byref(layout), channels, max_parallelism,
+                                                  N.NO_WATERMARK if watermark is None else int(watermark),
+                                                  ctypes.c_void_p(out.data_ptr()), cap, _ptr(off), _ptr(nb), None,
+                                                  ctypes.c_void_p(stream) if stream else None), self._h)
+        return out, list(zip(off.tolist(), nb.tolist()))
+
     def drain_late(self):
         """The late-data side output (flags=FLAG_LATE_SIDE_OUTPUT, WindowedStream.sideOutputLateData):
         the late records since the last call, as (key, timestamp, value bits) numpy columns."""

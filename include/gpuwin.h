@@ -436,6 +436,82 @@ int  gw_top_n_host(int64_t n, const int64_t* key, const int64_t* start, const in
                    int32_t top, int32_t mode, int64_t* key_out, int64_t* start_out, int64_t* end_out,
                    void* result_out, int64_t* win_rows_out, int64_t cap, int64_t* n_out);
 
+/* ---- network-buffer output: fired rows as serialized stream elements -------------
+ * The output side's counterpart of gw_ingest_serialized*: instead of columns that the JVM turns
+ * into one object per row and pushes through TimestampedCollector.collect and
+ * RecordWriter.serializeRecord, the rows leave as the bytes that path would have written, one
+ * contiguous range per downstream channel, ready for ResultPartitionWriter.emitRecord or for a
+ * second operator's gw_ingest_serialized_device on the same GPU.
+ *
+ * gw_row_layout: the emitted Tuple, field by field: where a field's 8 source bytes come from
+ * (GW_ROW_*) and its type.  'J': the source as a long.  'D': the source's IEEE bits unchanged
+ * (NaN payloads and -0.0 included), from GW_ROW_RESULT only.  'I': the low 32 bits of a source
+ * value that fits a Java int; one that does not fails the whole call with GW_E_RANGE (nothing is
+ * truncated; the output contents are then unspecified).  Every row becomes
+ *   be32 length | tag 0 (a record with timestamp) | be64 timestamp | the fields, big-endian
+ * (RecordWriter.java:144-156, StreamElementSerializer.java:163-197, TupleSerializer.java:135-144),
+ * gw_row_encoded_bytes(l) = 4 + 1 + 8 + the field widths bytes (< 0: an invalid layout).  The
+ * timestamp is end - 1 (emitWindowContents: setAbsoluteTimestamp(window.maxTimestamp()),
+ * WindowOperator.java:575-580); with GW_ENCODE_GLOBAL_WINDOW it is Long.MAX_VALUE
+ * (GlobalWindow.maxTimestamp()), for count-window rows whose start and end are ordinals.
+ * GW_E_INVALID: a field count outside 1..GW_MAX_FIELDS, an unknown source or type, 'D' from
+ * another source than the result, GW_ROW_PAYLOAD without a payload column.
+ *
+ * gw_encode_rows_device: stateless; n rows in device columns (d_payload may be NULL) to
+ * d_bytes[cap] in device memory (16-byte aligned).  channels == 1: the rows in input order.
+ * channels > 1 (a downstream keyBy on the row key, KeyGroupStreamPartitioner.selectChannel):
+ * row i goes to channel gw_operator_for_key_group(max_parallelism, channels,
+ * gw_key_group_for_hash(gw_java_long_hash(key[i]), max_parallelism)), a channel's rows keep
+ * their input order, and channel c's bytes are [chan_off[c], chan_off[c] + chan_bytes[c]) of
+ * d_bytes (host arrays of `channels` entries; starts are 16-byte aligned, the bytes between two
+ * ranges unspecified).  More than 128 channels: GW_E_UNSUPPORTED.  watermark != INT64_MIN: every
+ * channel's range ends with the serialized Watermark(watermark) (13 bytes), as the operator
+ * forwards the watermark to every channel behind the rows it fired; an empty channel then holds
+ * just the watermark.  cap too small: GW_E_OUTPUT_FULL with the needed size in chan_off[0] and
+ * nothing written.  No byte is ever written outside the reported ranges and their alignment
+ * padding.  n = 0: GW_OK, empty ranges (or watermarks only).  Waits on `stream` (the offsets go
+ * to the host), using scratch of its own per device.  Errors: gw_last_error of NULL.
+ * gw_encode_rows_host: the same contract as plain host code over host columns and bytes (any
+ * alignment): for a firing of a few rows, or a process without a device.
+ *
+ * gw_rows_serialized_device / gw_drain_serialized: the handle's pending rows (the view
+ * gw_rows_device gives: plain, window-class, session, count-window, first-element and minBy
+ * handles) encoded on the handle's stream; count-window handles get GW_ENCODE_GLOBAL_WINDOW,
+ * GW_ROW_PAYLOAD is valid on first-element / minBy handles only.  *n_rows (may be NULL): the
+ * rows encoded.  gw_rows_serialized_device writes d_bytes in device memory (16-byte aligned)
+ * behind the pending work of `stream` (the consumer's, which may still be using the buffer; NULL =
+ * the default stream), returns with the bytes complete, and leaves the rows pending: follow it
+ * with gw_clear_rows.  gw_drain_serialized copies the bytes to the host array and removes the
+ * rows on GW_OK; on any error they stay pending.  A handle fed a key_hash column carries keys
+ * whose hashCode the rows do not hold: channels > 1 is GW_E_UNSUPPORTED there (channels == 1
+ * works on every handle). */
+#define GW_ROW_KEY 0      /* row key                        */
+#define GW_ROW_START 1    /* window start                   */
+#define GW_ROW_END 2      /* window end                     */
+#define GW_ROW_RESULT 3   /* aggregate result (8 bytes)     */
+#define GW_ROW_PAYLOAD 4  /* first-element / minBy payload  */
+typedef struct gw_row_layout {
+    int32_t nfields;                 /* 1..GW_MAX_FIELDS fields of the emitted Tuple    */
+    int32_t source[GW_MAX_FIELDS];   /* GW_ROW_* per field                              */
+    char    types[GW_MAX_FIELDS];    /* 'J', 'D' or 'I'                                 */
+} gw_row_layout;
+#define GW_ENCODE_GLOBAL_WINDOW 1
+int64_t gw_row_encoded_bytes(const gw_row_layout* l);
+int  gw_encode_rows_device(int64_t n, const int64_t* d_key, const int64_t* d_start, const int64_t* d_end,
+                           const void* d_result, const int64_t* d_payload, const gw_row_layout* l, int32_t mode,
+                           int32_t channels, int32_t max_parallelism, int64_t watermark, void* d_bytes, int64_t cap,
+                           int64_t* chan_off, int64_t* chan_bytes, void* stream);
+int  gw_encode_rows_host(int64_t n, const int64_t* key, const int64_t* start, const int64_t* end, const void* result,
+                         const int64_t* payload, const gw_row_layout* l, int32_t mode, int32_t channels,
+                         int32_t max_parallelism, int64_t watermark, void* bytes, int64_t cap, int64_t* chan_off,
+                         int64_t* chan_bytes);
+int  gw_drain_serialized(gw_handle* h, const gw_row_layout* l, int32_t channels, int32_t max_parallelism,
+                         int64_t watermark, void* bytes, int64_t cap, int64_t* chan_off, int64_t* chan_bytes,
+                         int64_t* n_rows);
+int  gw_rows_serialized_device(gw_handle* h, const gw_row_layout* l, int32_t channels, int32_t max_parallelism,
+                               int64_t watermark, void* d_bytes, int64_t cap, int64_t* chan_off, int64_t* chan_bytes,
+                               int64_t* n_rows, void* stream);
+
 int64_t gw_late_dropped(const gw_handle* h);
 /* Late-data side output (GW_FLAG_LATE_SIDE_OUTPUT; WindowedStream.sideOutputLateData, RS/api/
  * datastream/WindowedStream.java): the records WindowOperator.processElement skips as late

@@ -116,7 +116,60 @@ public class GpuWindowOperator<IN, K>
     static { System.loadLibrary("gpuwin_jni"); }
 
     /** What one fired (key, window, result) row becomes (see the class comment). */
-    public enum OutputMode { POSITIONAL, MIN_MAX_BY, AGGREGATE, KEYED_WINDOW, WINDOW_FUNCTION }
+    public enum OutputMode { POSITIONAL, MIN_MAX_BY, AGGREGATE, KEYED_WINDOW, WINDOW_FUNCTION, SERIALIZED }
+
+    /**
+     * OutputMode.SERIALIZED: where the fired rows' bytes go.  The task wires this to its
+     * ResultPartitionWriter (emitRecord(ByteBuffer, subpartition), which copies the bytes into the
+     * subpartition's buffers, spanning them as needed); the slice holds length-prefixed stream
+     * elements: the channel's rows and, last, the watermark that fired them.
+     */
+    public interface SerializedOutput {
+        int numberOfChannels();
+        int maxParallelism();
+        void emit(ByteBuffer elements, int channel) throws java.io.IOException;
+    }
+
+    // OutputMode.SERIALIZED (setSerializedOutput): the emitted Tuple as gw_row_layout, its sink and buffers
+    private SerializedOutput serializedOutput;
+    private String rowTypes;
+    private int[] rowSources;
+    private ByteBuffer serBytes;
+    private java.nio.LongBuffer serRanges;
+
+    /** Emit fired rows as serialized Tuples of the given fields ('J', 'D', 'I' from GW_ROW_* sources,
+     *  include/gpuwin.h gw_row_layout) straight to the partition writer.  Long keys only: with
+     *  more than one channel the library derives a row's channel from Long.hashCode(key). */
+    public void setSerializedOutput(SerializedOutput out, String types, int[] sources) {
+        this.serializedOutput = out;
+        this.rowTypes = types;
+        this.rowSources = sources.clone();
+        this.serRanges = ByteBuffer.allocateDirect(16 * out.numberOfChannels())
+                .order(java.nio.ByteOrder.nativeOrder()).asLongBuffer();
+    }
+
+    /** Drain every pending row through gw_drain_serialized and hand each channel its slice; the
+     *  watermark (Long.MIN_VALUE: none) travels behind the rows inside the slices. */
+    private void emitSerialized(long watermark) throws Exception {
+        final int channels = serializedOutput.numberOfChannels();
+        long cap = serBytes == null ? 1 << 20 : serBytes.capacity();
+        long rows;
+        while (true) {
+            if (serBytes == null || serBytes.capacity() < cap) serBytes = ByteBuffer.allocateDirect((int) cap);
+            rows = nativeDrainSerialized(handle, serBytes, serBytes.capacity(), rowTypes, rowSources, channels,
+                    serializedOutput.maxParallelism(), watermark, serRanges);
+            if (rows >= 0) break;
+            cap = Math.max(-rows, 2 * cap);  // too small: the needed size came back negated
+            if (cap > Integer.MAX_VALUE) throw new IllegalStateException("fired rows exceed one direct buffer");
+        }
+        for (int c = 0; c < channels; c++) {
+            final int off = (int) serRanges.get(2 * c), len = (int) serRanges.get(2 * c + 1);
+            if (len == 0) continue;
+            ByteBuffer slice = serBytes.duplicate();
+            slice.position(off).limit(off + len);
+            serializedOutput.emit(slice.slice(), c);
+        }
+    }
 
     // gw_assigner / gw_trigger / gw_agg codes of include/gpuwin.h
     private static final int GW_SESSION = 2, GW_COUNT_TUMBLING = 3, GW_COUNT_SLIDING = 4, GW_SESSION_DYNAMIC = 5;
@@ -670,8 +723,10 @@ public class GpuWindowOperator<IN, K>
         flush();
         currentWm = mark.getTimestamp();
         nativeAdvanceWatermark(handle, mark.getTimestamp());
-        emitRows();
+        if (serializedOutput != null) emitSerialized(mark.getTimestamp());  // rows, then the watermark, as bytes
+        else emitRows();
         if (wide()) releaseElements(mark.getTimestamp());
+        if (serializedOutput != null) return;  // (the watermark went out inside the slices)
         super.processWatermark(mark);  // forward after the fired rows
     }
 
@@ -784,6 +839,10 @@ public class GpuWindowOperator<IN, K>
     private static native void nativeRemapKeys(byte[] blob, long[] from, long[] to);
     private static native long[] nativeSnapshotPayloads(byte[] blob, long[] maxEnd);
     private static native void nativeRemapPayloads(byte[] blob, long[] from, long[] to);
+    /** gw_drain_serialized: the rows drained, or -(bytes needed) when cap is too small. */
+    private static native long nativeDrainSerialized(long h, ByteBuffer bytes, long cap, String types, int[] sources,
+                                                     int channels, int maxParallelism, long watermark,
+                                                     java.nio.LongBuffer ranges);
     private static native int nativeDrainLate(long h, ByteBuffer key, ByteBuffer ts, ByteBuffer value, int cap);
     /** The keyBy exchange's receive columns (GpuKeyByExchange.batch, produced on `stream`)
      *  straight into the operator. */

@@ -330,6 +330,54 @@ JNIEXPORT void JNICALL CLS(nativeRemapPayloads)(JNIEnv* env, jclass c, jbyteArra
     fail(env, 0, rc);
 }
 
+/* ---- network-buffer output (gw_drain_serialized) ----------------------------------------
+ * bytes:  a direct ByteBuffer of cap bytes: the channels' serialized rows.
+ * types / sources: the emitted Tuple (gw_row_layout): one JVM type code and one GW_ROW_* per field.
+ * ranges: a direct LongBuffer of 2 * channels longs: (offset, length) of every channel's bytes.
+ * Returns the rows drained.  A buffer too small returns -(needed bytes) and drains nothing, so
+ * the caller grows the buffer and calls again; every other error throws, the rows stay pending.
+ * The only glue that reads an int[]: the test-only jni.h of tests/jni/ declares no int[] access
+ * and leaves this function out; tests/jni/rowenc/ has the header that compiles it. */
+#ifndef GW_TEST_JNI_H
+JNIEXPORT jlong JNICALL CLS(nativeDrainSerialized)(JNIEnv* env, jclass c, jlong h, jobject bytes, jlong cap,
+                                                   jstring types, jintArray sources, jint channels,
+                                                   jint maxParallelism, jlong watermark, jobject ranges) {
+    gw_handle* g = (gw_handle*)(intptr_t)h;
+    gw_row_layout lay;
+    memset(&lay, 0, sizeof lay);
+    const char* t = (*env)->GetStringUTFChars(env, types, 0);
+    const size_t nt = t ? strlen(t) : 0;
+    const jsize ns = (*env)->GetArrayLength(env, sources);
+    const int ok = t && nt >= 1 && nt <= GW_MAX_FIELDS && (size_t)ns == nt && channels >= 1 && channels <= 128;
+    if (ok) {
+        jint src[GW_MAX_FIELDS];
+        (*env)->GetIntArrayRegion(env, sources, 0, ns, src);
+        lay.nfields = (int32_t)nt;
+        for (size_t i = 0; i < nt; ++i) {
+            lay.types[i] = t[i];
+            lay.source[i] = src[i];
+        }
+    }
+    if (t) (*env)->ReleaseStringUTFChars(env, types, t);
+    if (!ok) {
+        jclass ex = (*env)->FindClass(env, "java/lang/IllegalArgumentException");
+        (*env)->ThrowNew(env, ex, "nativeDrainSerialized: one source per field, 1..8 fields, 1..128 channels");
+        return 0;
+    }
+    int64_t off[128], len[128], rows = 0;
+    const int rc = gw_drain_serialized(g, &lay, channels, maxParallelism, watermark,
+                                       (*env)->GetDirectBufferAddress(env, bytes), cap, off, len, &rows);
+    if (rc == GW_E_OUTPUT_FULL) return -off[0];
+    if (fail(env, g, rc) < 0) return 0;
+    int64_t* r = (*env)->GetDirectBufferAddress(env, ranges);
+    for (jint q = 0; q < channels; ++q) {
+        r[2 * q] = off[q];
+        r[2 * q + 1] = len[q];
+    }
+    return rows;
+}
+#endif
+
 /* ---- GpuKeyByExchange: the keyBy shuffle through libgpuwin's RCCL communicator ---- */
 #define XCLS(n) Java_org_apache_flink_streaming_runtime_operators_windowing_gpu_GpuKeyByExchange_##n
 
