@@ -64,6 +64,8 @@ EXPORTS = [
     "gw_ingest_gap", "gw_ingest_gap_device",
     "gw_row_encoded_bytes", "gw_encode_rows_device", "gw_encode_rows_host", "gw_drain_serialized",
     "gw_rows_serialized_device",
+    "gw_valve_create", "gw_valve_destroy", "gw_valve_input", "gw_decode_channels_device",
+    "gw_set_input_channels", "gw_ingest_channels", "gw_ingest_channels_device", "gw_input_status",
 ]
 EXCHANGE_ID_BYTES = 128
 EXCHANGE_RECV_SETS = 3  # gpuwin.h GW_EXCHANGE_RECV_SETS
@@ -78,6 +80,23 @@ class GwRecordLayout(ctypes.Structure):
 class GwDecodeResult(ctypes.Structure):
     _fields_ = [("records", ctypes.c_int64), ("watermarks", ctypes.c_int64), ("consumed", ctypes.c_int64),
                 ("skipped", ctypes.c_int64)]
+
+
+class GwValveOutput(ctypes.Structure):
+    """gw_valve_output: what one input of a gw_valve emitted."""
+    _fields_ = [("has_watermark", ctypes.c_int32), ("has_status", ctypes.c_int32), ("watermark", ctypes.c_int64),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class GwDecodeChannelsResult(ctypes.Structure):
+    _fields_ = [("records", ctypes.c_int64), ("events", ctypes.c_int64), ("skipped", ctypes.c_int64),
+                ("error_range", ctypes.c_int32), ("reserved", ctypes.c_int32), ("error_pos", ctypes.c_int64)]
+
+
+# gpuwin.h GW_EVENT_* / GW_STATUS_*: the events of an input channel that its valve takes
+EVENT_WATERMARK, EVENT_STATUS = 0, 1
+STATUS_ACTIVE, STATUS_IDLE = 0, -1
+MAX_INPUT_CHANNELS = 1024
 
 
 def record_layout(types: str, key_field: int, value_field: int = -1) -> GwRecordLayout:
@@ -268,6 +287,15 @@ def lib() -> ctypes.CDLL:
                                         p, p]),
         "gw_drain_serialized": (c_int, [p, ctypes.POINTER(GwRowLayout), i32, i32, i64, p, i64, p, p, P64]),
         "gw_rows_serialized_device": (c_int, [p, ctypes.POINTER(GwRowLayout), i32, i32, i64, p, i64, p, p, P64, p]),
+        "gw_valve_create": (c_int, [i32, ctypes.POINTER(p)]),
+        "gw_valve_destroy": (c_int, [p]),
+        "gw_valve_input": (c_int, [p, i32, i32, i64, ctypes.POINTER(GwValveOutput)]),
+        "gw_decode_channels_device": (c_int, [i32, p, p, ctypes.POINTER(GwRecordLayout), p, p, p, i64, p, p, p, i64,
+                                              p, p, p, ctypes.POINTER(GwDecodeChannelsResult), p]),
+        "gw_set_input_channels": (c_int, [p, i32]),
+        "gw_ingest_channels": (c_int, [p, i32, p, p, p, ctypes.POINTER(GwRecordLayout), p, P64]),
+        "gw_ingest_channels_device": (c_int, [p, i32, p, p, p, ctypes.POINTER(GwRecordLayout), p, p, P64]),
+        "gw_input_status": (c_int, [p, P64, ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -56,4 +56,34 @@ hipError_t launch_nb_decode(const uint8_t* buf, int64_t nbytes, const NbLayout& 
                             int64_t* val, int64_t rec_cap, int64_t* wm_pos, int64_t* wm_val, int64_t wm_cap,
                             void* scratch, NbStatus* d_st, hipStream_t s);
 
+// ---- segmented decode: many byte ranges (input channels) in one pipeline run ----
+// Every range starts on a chunk of its own, so the chunks of all ranges form one virtual
+// stream: range r's byte b stands at virtual position first[r] * kNbChunk + b, where first[r]
+// is the number of chunks of the ranges before it.  Positions, error ranks and the scans work
+// on virtual positions; only where a chunk's bytes lie and where they end comes from a
+// per-chunk descriptor (k_nb_desc builds them on the device from the range table).
+struct NbRange {
+    const uint8_t* ptr;  // device pointer, 4-byte aligned
+    int64_t len;         // bytes (0 allowed)
+    int64_t first;       // index of the range's first chunk (nb_seg_plan fills it)
+};
+struct NbChunkDesc {
+    const uint8_t* ptr;  // the chunk's first byte
+    int64_t left;        // bytes from there to the end of its range
+    int32_t range;       // the range it belongs to
+    int32_t first;       // the range's first chunk (== this chunk: chains enter at byte 0)
+};
+// Sets ranges[r].first; returns the total chunk count, or -1 where it exceeds what a descriptor holds.
+int64_t nb_seg_plan(NbRange* ranges, int32_t nranges);
+int64_t nb_seg_scratch_bytes(int64_t nchunks, int32_t nranges);
+// ranges: host memory that stays valid until the stream has run (pinned for an asynchronous
+// copy), `first` set by nb_seg_plan.  d_rng: 3 * nranges words, written as consumed[r] |
+// first record of range r | first event of range r (the latter two only for ranges with bytes).
+// Events: ev_pos (records of the whole call before it), ev_kind (0 watermark, 1 watermark
+// status), ev_val; d_st->watermarks counts them all.
+hipError_t launch_nb_decode_seg(const NbRange* ranges, int32_t nranges, int64_t nchunks, const NbLayout& L,
+                                int64_t* key, int64_t* ts, int64_t* val, int64_t rec_cap, int64_t* ev_pos,
+                                int32_t* ev_kind, int64_t* ev_val, int64_t ev_cap, void* scratch, NbStatus* d_st,
+                                int64_t* d_rng, hipStream_t s);
+
 }  // namespace gw

@@ -51,18 +51,44 @@ __device__ __forceinline__ int64_t nb_pos(int64_t w) { return w & (((int64_t)1 <
 __device__ __forceinline__ int nb_state(int64_t w) { return (int)(w >> 56); }
 constexpr int64_t kNonConv = -1;
 
-// A wave's chunk in flight: bytes [base, base + 4*kNbWords) ∩ [0, nbytes) as dwords in
+// Geometry: where chunk c's bytes lie, how many bytes are left from its start to the end of
+// its stream, and which chunk the stream's chain enters.  NbFlat is the single stream (chunk c
+// = bytes [c * kNbChunk, ...) of one buffer; everything folds to the plain index arithmetic),
+// NbSeg reads a per-chunk descriptor (gw_netbuf.h): each range is a stream of its own whose
+// chain enters at its first chunk, and nothing is read past a range's end.
+struct NbFlat {
+    static constexpr bool kSeg = false;
+    const uint8_t* buf;
+    int64_t nbytes;
+    __device__ __forceinline__ const uint8_t* bytes(int64_t c) const { return buf + c * kNbChunk; }
+    __device__ __forceinline__ int64_t left(int64_t c) const { return nbytes - c * kNbChunk; }
+    __device__ __forceinline__ int64_t first(int64_t) const { return 0; }
+    __device__ __forceinline__ void set_consumed(NbStatus* st, int64_t, int64_t pos) const { st->consumed = pos; }
+};
+struct NbSeg {
+    static constexpr bool kSeg = true;
+    const NbChunkDesc* d;
+    int64_t* rng;      // consumed | first record | first event, nranges each
+    int32_t* ev_kind;
+    int32_t nranges;
+    __device__ __forceinline__ const uint8_t* bytes(int64_t c) const { return d[c].ptr; }
+    __device__ __forceinline__ int64_t left(int64_t c) const { return d[c].left; }
+    __device__ __forceinline__ int64_t first(int64_t c) const { return d[c].first; }
+    __device__ __forceinline__ void set_consumed(NbStatus*, int64_t c, int64_t pos) const {
+        rng[d[c].range] = pos - (int64_t)d[c].first * kNbChunk;
+    }
+};
+
+// A wave's chunk in flight: the first min(left, 4*kNbWords) bytes from cb as dwords in
 // registers (kNbRegs per lane; bytes past the end read as 0), loaded one chunk ahead of
 // the walk so the HBM latency hides behind the LDS chain walk of the current chunk.
 template <int NL>
 constexpr int nb_regs() { return (nb_words<NL>() + 63) / 64; }
 template <int NL>
-__device__ __forceinline__ void nb_fetch(uint32_t (&r)[nb_regs<NL>()], const uint8_t* buf, int64_t base,
-                                         int64_t nbytes) {
+__device__ __forceinline__ void nb_fetch(uint32_t (&r)[nb_regs<NL>()], const uint8_t* cb, int64_t left) {
     constexpr int kNbWords = nb_words<NL>(), kNbRegs = nb_regs<NL>();
     const int lane = __lane_id();
-    const int64_t left = nbytes - base;
-    const uint32_t* src = (const uint32_t*)(buf + base);  // base is a multiple of kNbChunk; buf 4-aligned
+    const uint32_t* src = (const uint32_t*)cb;  // the chunk's first byte: 4-aligned
     if (left >= 4 * (int64_t)(64 * kNbRegs)) {  // the whole register window is in range (wave-uniform)
 #pragma unroll
         for (int k = 0; k < kNbRegs; ++k) r[k] = __builtin_nontemporal_load(src + lane + 64 * k);
@@ -77,7 +103,7 @@ __device__ __forceinline__ void nb_fetch(uint32_t (&r)[nb_regs<NL>()], const uin
         if (i < full) {
             v = __builtin_nontemporal_load(src + i);
         } else if (i == full) {
-            for (int b = 0; b < (avail & 3); ++b) v |= (uint32_t)buf[base + 4 * i + b] << (8 * b);
+            for (int b = 0; b < (avail & 3); ++b) v |= (uint32_t)cb[4 * i + b] << (8 * b);
         }
         r[k] = v;
     }
@@ -111,6 +137,7 @@ __device__ __forceinline__ uint64_t lds_be64(const uint32_t* w, int p) {
 // One candidate's walk from its state (pos, counts, st) while pos < H, out of LDS.
 // Branch-free step (one ds_read2 gives the length word and the tag): every lane steps in
 // lockstep under a full exec mask, and the per-step VALU count stays small.
+template <bool kStatusEvents>
 __device__ __forceinline__ void nb_walk_lane(const uint32_t* l, int H, int rlim, int rec_ts, int rec_nots, bool run,
                                              int& pos, uint32_t& cnt, int& st) {
     while (__ballot(run)) {
@@ -138,8 +165,9 @@ __device__ __forceinline__ void nb_walk_lane(const uint32_t* l, int H, int rlim,
         const bool adv = run && ns == kStNormal;
         st = (run && !adv) ? ns : st;
         // records | watermarks << 16 in one word: 2-bit class per tag (0, 1: record; 2, 6:
-        // watermark; 3-5: skipped), from a packed table
-        const uint32_t cls = (0x2025u >> (2 * (tag & 7u))) & 3u;
+        // watermark; 3-5: skipped), from a packed table; the segmented decode counts a
+        // WatermarkStatus (4) with the watermarks: both are events of its valve
+        const uint32_t cls = ((kStatusEvents ? 0x2225u : 0x2025u) >> (2 * (tag & 7u))) & 3u;
         cnt += adv ? ((cls & 1u) | ((cls & 2u) << 15)) : 0u;
         pos = adv ? p + 4 + len : pos;
         run = adv && pos < H;
@@ -155,8 +183,8 @@ __device__ __forceinline__ void nb_walk_lane(const uint32_t* l, int H, int rlim,
 // chunk's end with one thread.  Otherwise (a payload that mimics a chain for longer, the
 // stream's last chunk) the wave loads the whole chunk and walks on to its end, as before.
 // Per candidate: exit (relative position | state << 28) and (records | watermarks << 16).
-template <int NL>
-__global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nbytes, int64_t nch, int32_t vbytes,
+template <int NL, class G>
+__global__ void __launch_bounds__(256) k_nb_walk(const G g, int64_t nch, int32_t vbytes,
                                                  uint32_t* exits, uint32_t* cnt, int64_t* conv, int64_t* sync,
                                                  NbStatus* nst) {
     constexpr int kNbWords = nb_words<NL>(), CPL = NL / 64;
@@ -167,9 +195,11 @@ __global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nby
     const int w = threadIdx.x >> 6, lane = __lane_id();
     const int64_t stride = (int64_t)gridDim.x * kNbWaves;
     uint32_t pre[kSyncRegs];
-    auto fetch_window = [&](int64_t b) {  // the sync window's dwords (bytes past the end read as 0)
-        const int64_t left = nbytes - b;
-        const uint32_t* src = (const uint32_t*)(buf + b);
+    int64_t pleft = 0;  // the fetched chunk's bytes left
+    auto fetch_window = [&](int64_t cc) {  // the sync window's dwords (bytes past the end read as 0)
+        const int64_t left = pleft = g.left(cc);
+        const uint8_t* cb = g.bytes(cc);
+        const uint32_t* src = (const uint32_t*)cb;
         if (left >= 4 * (int64_t)(64 * kSyncRegs)) {  // in range (wave-uniform)
 #pragma unroll
             for (int k = 0; k < kSyncRegs; ++k)
@@ -185,13 +215,13 @@ __global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nby
                 v = __builtin_nontemporal_load(src + i);
             } else {
                 for (int q = 0; q < 4; ++q)
-                    if (4 * (int64_t)i + q < left) v |= (uint32_t)buf[b + 4 * i + q] << (8 * q);
+                    if (4 * (int64_t)i + q < left) v |= (uint32_t)cb[4 * i + q] << (8 * q);
             }
             pre[k] = v;
         }
     };
     int64_t c = (int64_t)blockIdx.x * kNbWaves + w;
-    if (c < nch) fetch_window(c * kNbChunk);
+    if (c < nch) fetch_window(c);
     for (; c < nch; c += stride) {
     const int64_t base = c * kNbChunk;
     __builtin_amdgcn_wave_barrier();  // the previous chunk's LDS reads are done
@@ -200,9 +230,10 @@ __global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nby
         if (lane + 64 * k < kSyncWords) lds[w][lane + 64 * k] = pre[k];
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (c + stride < nch) fetch_window((c + stride) * kNbChunk);
+    int64_t left = pleft;  // (a descriptor's value came with the chunk's own prefetch)
+    if (c + stride < nch) fetch_window(c + stride);
+    if constexpr (!G::kSeg) left = g.left(c);
     const uint32_t* l = lds[w];
-    const int64_t left = nbytes - base;
     const int rlim = left < kNbChunk + 4 * NL ? (int)left : kNbChunk + 4 * NL;  // binding only near the end
     const int rend = rlim < kNbChunk ? rlim : kNbChunk;
     const bool windowed = rend > kSync;
@@ -212,7 +243,7 @@ __global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nby
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
         pos[k] = lane + 64 * k; cn[k] = 0; st[k] = kStNormal;
-        nb_walk_lane(l, H, rlim, rec_ts, rec_nots, pos[k] < H, pos[k], cn[k], st[k]);
+        nb_walk_lane<G::kSeg>(l, H, rlim, rec_ts, rec_nots, pos[k] < H, pos[k], cn[k], st[k]);
     }
     // converged: every live candidate stopped normally on the same position
     bool conv_ok = windowed;
@@ -239,14 +270,14 @@ __global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nby
     if (windowed && !conv_ok) {  // walk on to the chunk's end out of the whole chunk
         if (lane == 0) atomicAdd(&nst->fallback, 1ull);
         uint32_t full[nb_regs<NL>()];
-        nb_fetch<NL>(full, buf, base, nbytes);
+        nb_fetch<NL>(full, g.bytes(c), left);
         __builtin_amdgcn_wave_barrier();
         nb_put<NL>(lds[w], full);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int k = 0; k < CPL; ++k)
-            nb_walk_lane(l, rend, rlim, rec_ts, rec_nots, st[k] == kStNormal && pos[k] < rend, pos[k], cn[k], st[k]);
+            nb_walk_lane<G::kSeg>(l, rend, rlim, rec_ts, rec_nots, st[k] == kStNormal && pos[k] < rend, pos[k], cn[k], st[k]);
     }
     int64_t ex[CPL];
     bool live[CPL];
@@ -290,8 +321,8 @@ __global__ void __launch_bounds__(256) k_nb_walk(const uint8_t* buf, int64_t nby
 // Pass 1b: one thread per synced chunk walks the true chain from its sync point P to the
 // chunk's end (global loads; each thread streams through its own chunk), the exit and the
 // record / watermark counts of [P, exit) -> conv[c], tcnt[c], the element starts -> tmask.
-template <int NL>
-__global__ void __launch_bounds__(256) k_nb_tail(const uint8_t* buf, int64_t nbytes, int64_t nch, int32_t vbytes,
+template <int NL, class G>
+__global__ void __launch_bounds__(256) k_nb_tail(const G g, int64_t nch, int32_t vbytes,
                                                  const int64_t* sync, int64_t* conv, uint32_t* tcnt,
                                                  uint32_t* tmask) {
     // element starts of [P, exit) as a bit mask per chunk (kNbMaskWords words), which
@@ -307,10 +338,10 @@ __global__ void __launch_bounds__(256) k_nb_tail(const uint8_t* buf, int64_t nby
         const int64_t s0 = c < nch ? sync[c] : -1;
         if (s0 >= 0) {
             const int64_t base = c * kNbChunk;
-            const int64_t left = nbytes - base;
+            const int64_t left = g.left(c);
             const int rlim = left < kNbChunk + 4 * NL ? (int)left : kNbChunk + 4 * NL;
             const int rend = rlim < kNbChunk ? rlim : kNbChunk;
-            const uint8_t* b = buf + base;
+            const uint8_t* b = g.bytes(c);
             int pos = (int)(s0 - base), nr = 0, nw = 0, st = kStNormal, mw = 0;
             uint32_t cur = 0;
             while (pos < rend) {
@@ -336,7 +367,7 @@ __global__ void __launch_bounds__(256) k_nb_tail(const uint8_t* buf, int64_t nby
                              : len != want ? kStDead : kStNormal;
                 if (ns != kStNormal) { st = ns; break; }
                 nr += tag <= 1u ? 1 : 0;
-                nw += (tag == 2u || tag == 6u) ? 1 : 0;
+                nw += (tag == 2u || tag == 6u || (G::kSeg && tag == 4u)) ? 1 : 0;
                 for (; mw < (pos >> 5); ++mw, cur = 0) mk[mw] = cur;
                 cur |= 1u << (pos & 31);
                 pos += 4 + len;
@@ -367,8 +398,8 @@ __device__ __forceinline__ int64_t nb_exit_word(const uint32_t* exits, const int
 
 // Pass 2: one thread per chunk finds its true entry from the nearest earlier chunk with a
 // unique exit, then the block scans the chunk counts (exclusive, block-local).
-template <int NL>
-__global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(int64_t nbytes, int64_t nch, const uint32_t* exits,
+template <int NL, class G>
+__global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(const G g, int64_t nch, const uint32_t* exits,
                                                              const uint32_t* cnt, const int64_t* conv,
                                                              const int64_t* sync, const uint32_t* tcnt, int64_t* entry,
                                                              int32_t* offs, long long* btot, NbStatus* st) {
@@ -376,10 +407,12 @@ __global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(int64_t nbytes, int
     const int64_t c = (int64_t)blockIdx.x * kNbScanBlock + threadIdx.x;
     int nr = 0, nw = 0;
     if (c < nch) {
+        // the stream's chain enters its first chunk f at byte 0; the walk back stops there
+        const int64_t f = g.first(c), end = c * kNbChunk + g.left(c);
         int64_t j = c - 1;
-        while (j >= 0 && conv[j] == kNonConv) --j;
+        while (j >= f && conv[j] == kNonConv) --j;
         if (j < c - 1) atomicAdd(&st->walkback, (unsigned long long)(c - 1 - j));
-        int64_t e = j < 0 ? nb_pack(0, kStNormal) : conv[j];  // entry word of chunk j + 1
+        int64_t e = j < f ? nb_pack(f * kNbChunk, kStNormal) : conv[j];  // entry word of chunk j + 1
         for (int64_t t = j + 1; t < c && nb_state(e) == kStNormal; ++t) {
             const int64_t lane = nb_pos(e) - t * kNbChunk;
             if (lane < 0 || lane >= NL) { e = nb_pack(nb_pos(e), kStDead); break; }
@@ -389,7 +422,7 @@ __global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(int64_t nbytes, int
         if (nb_state(e) == kStNormal) {
             const int64_t p = nb_pos(e);
             const int64_t lane = p - c * kNbChunk;
-            if (p >= nbytes) {
+            if (p >= end) {
                 // the chain ended exactly at the end of the bytes: nothing starts here
             } else if (lane < 0 || lane >= NL) {
                 atomicMax(&st->corrupt, nb_error_rank(p));
@@ -410,8 +443,8 @@ __global__ void __launch_bounds__(kNbScanBlock) k_nb_resolve(int64_t nbytes, int
                 // the chunks behind it may decode again from a later unique exit and raise others
                 if (s == kStDead) atomicMax(&st->corrupt, nb_error_rank(nb_pos(ex)));
                 if (s == kStLong) atomicMax(&st->unsupported, nb_error_rank(nb_pos(ex)));
-                if (s == kStTail) st->consumed = nb_pos(ex);  // at most one chunk of the chain stops early
-                if (s == kStNormal && nb_pos(ex) >= nbytes) st->consumed = nbytes;
+                if (s == kStTail) g.set_consumed(st, c, nb_pos(ex));  // at most one chunk of the chain stops early
+                if (s == kStNormal && nb_pos(ex) >= end) g.set_consumed(st, c, end);
             }
         }
         entry[c] = ent;
@@ -483,8 +516,8 @@ __device__ __forceinline__ int64_t nb_field(const uint32_t* l, int p, int type) 
 }
 
 // Pass 4: each chunk's true chain, walked once more out of LDS, decoded by all 64 lanes.
-template <int NL>
-__global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t nbytes, int64_t nch, NbLayout L,
+template <int NL, class G>
+__global__ void __launch_bounds__(256) k_nb_decode(const G g, int64_t nch, NbLayout L,
                                                    const int64_t* entry, const int32_t* offs, const long long* btot,
                                                    const int64_t* sync, const uint32_t* tmask,
                                                    int64_t* key, int64_t* ts, int64_t* val, int64_t rec_cap,
@@ -497,9 +530,10 @@ __global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t n
     const int64_t stride = (int64_t)gridDim.x * kNbWaves;
     uint32_t pre[kNbRegs];
     // the next chunk's entry, sync point, mask word and output offsets load with its bytes
-    int64_t pe0 = -1, psy = -1, prb = 0, pwb = 0;
+    int64_t pe0 = -1, psy = -1, prb = 0, pwb = 0, plf = 0;
     uint32_t pmw = 0;
     auto fetch_meta = [&](int64_t cc) {
+        plf = g.left(cc);
         pe0 = entry[cc];
         psy = sync[cc];
         pmw = lane < kNbMaskWords ? tmask[cc * kNbMaskWords + lane] : 0u;
@@ -509,25 +543,31 @@ __global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t n
     };
     int64_t c = (int64_t)blockIdx.x * kNbWaves + w;
     if (c < nch) {
-        nb_fetch<NL>(pre, buf, c * kNbChunk, nbytes);
         fetch_meta(c);
+        nb_fetch<NL>(pre, g.bytes(c), plf);
     }
     for (; c < nch; c += stride) {
     const int64_t e0 = pe0, sy = psy;
     const uint32_t mword = pmw;
     int64_t rbase = prb, wbase = pwb;
-    const int64_t base = c * kNbChunk;
+    const int64_t base = c * kNbChunk, left = G::kSeg ? plf : g.left(c);
     __builtin_amdgcn_wave_barrier();  // the previous chunk's LDS reads are done
     nb_put<NL>(lds[w], pre);
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (c + stride < nch) {
-        nb_fetch<NL>(pre, buf, (c + stride) * kNbChunk, nbytes);
         fetch_meta(c + stride);
+        nb_fetch<NL>(pre, g.bytes(c + stride), plf);
+    }
+    if constexpr (G::kSeg) {  // a range's first chunk: where its records and events start
+        if (lane == 0 && g.first(c) == c) {
+            const int32_t r = g.d[c].range;
+            g.rng[g.nranges + r] = rbase;
+            g.rng[2 * g.nranges + r] = wbase;
+        }
     }
     if (e0 < 0) continue;
     const uint32_t* l = lds[w];
-    const int64_t left = nbytes - base;
     const int rlim = left < kNbChunk + 4 * NL ? (int)left : kNbChunk + 4 * NL;
     const int rend = rlim < kNbChunk ? rlim : kNbChunk;
     {  // the true chain, walked by the whole wave in lockstep (uniform addresses: LDS
@@ -588,6 +628,9 @@ __global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t n
             } else if (tag == 2 || tag == 6) {
                 kind = 2;
                 ok = len == (tag == 2 ? 9 : 13);
+            } else if (G::kSeg && tag == 4) {  // WatermarkStatus: an event of the valve
+                kind = 2;
+                ok = len == 5;
             } else if (tag == 3 || tag == 4 || tag == 5) {
                 kind = 3;
                 ok = len == (tag == 3 ? 29 : tag == 4 ? 5 : 2);
@@ -615,7 +658,13 @@ __global__ void __launch_bounds__(256) k_nb_decode(const uint8_t* buf, int64_t n
             if (o < wm_cap) {
                 // records before the watermark: all earlier chunks', earlier rounds', lower lanes'
                 wm_pos[o] = rbase + __popcll(br & below);
-                wm_val[o] = (int64_t)lds_be64(l, p + (tag == 2 ? 5 : 9));
+                if constexpr (G::kSeg) {
+                    g.ev_kind[o] = tag == 4 ? 1 : 0;
+                    wm_val[o] = tag == 4 ? (int64_t)(int32_t)lds_be32(l, p + 5)
+                                         : (int64_t)lds_be64(l, p + (tag == 2 ? 5 : 9));
+                } else {
+                    wm_val[o] = (int64_t)lds_be64(l, p + (tag == 2 ? 5 : 9));
+                }
             } else {
                 full = 1;
             }
@@ -640,12 +689,11 @@ int64_t nb_scratch_bytes(int64_t nbytes) {
     return nch * kNbMaxLanes * 8 + nch * (40 + 4 * kNbMaskWords) + nblk * 16 + 256;
 }
 
-hipError_t launch_nb_decode(const uint8_t* buf, int64_t nbytes, const NbLayout& L, int64_t* key, int64_t* ts,
-                            int64_t* val, int64_t rec_cap, int64_t* wm_pos, int64_t* wm_val, int64_t wm_cap,
-                            void* scratch, NbStatus* d_st, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(d_st, 0, sizeof(NbStatus), s);
-    if (e != hipSuccess || nbytes <= 0) return e;
-    const int64_t nch = (nbytes + kNbChunk - 1) / kNbChunk;
+// The five passes over nch chunks of geometry g; the scratch is nb_scratch_bytes(nch * kNbChunk).
+template <class G>
+static hipError_t nb_launch(const G& g, int64_t nch, const NbLayout& L, int64_t* key, int64_t* ts, int64_t* val,
+                            int64_t rec_cap, int64_t* wm_pos, int64_t* wm_val, int64_t wm_cap, void* scratch,
+                            NbStatus* d_st, hipStream_t s) {
     const int64_t nblk = (nch + kNbScanBlock - 1) / kNbScanBlock;
     uint8_t* p = (uint8_t*)scratch;
     uint32_t* exits = (uint32_t*)p;            p += nch * kNbMaxLanes * 4;
@@ -677,14 +725,14 @@ hipError_t launch_nb_decode(const uint8_t* buf, int64_t nbytes, const NbLayout& 
     // timestamp: 4 + 1 + 8 + vbytes; the other tags are at most 33 bytes)
     const bool wide = 13 + L.vbytes > 64;
 #define NB_LAUNCH(NL)                                                                                              \
-    hipLaunchKernelGGL(k_nb_walk<NL>, dim3((unsigned)gb), dim3(256), 0, s, buf, nbytes, nch, L.vbytes, exits, cnt, \
+    hipLaunchKernelGGL((k_nb_walk<NL, G>), dim3((unsigned)gb), dim3(256), 0, s, g, nch, L.vbytes, exits, cnt,      \
                        conv, sync, d_st);                                                                          \
-    hipLaunchKernelGGL(k_nb_tail<NL>, dim3((unsigned)tb), dim3(256), 0, s, buf, nbytes, nch,                       \
+    hipLaunchKernelGGL((k_nb_tail<NL, G>), dim3((unsigned)tb), dim3(256), 0, s, g, nch,                            \
                        L.vbytes, sync, conv, tcnt, tmask);                                                         \
-    hipLaunchKernelGGL(k_nb_resolve<NL>, dim3((unsigned)nblk), dim3(kNbScanBlock), 0, s, nbytes, nch, exits, cnt,  \
+    hipLaunchKernelGGL((k_nb_resolve<NL, G>), dim3((unsigned)nblk), dim3(kNbScanBlock), 0, s, g, nch, exits, cnt,  \
                        conv, sync, tcnt, entry, offs, btot, d_st);                                                 \
     hipLaunchKernelGGL(k_nb_scan, dim3(1), dim3(1024), 0, s, nblk, btot, d_st);                                    \
-    hipLaunchKernelGGL(k_nb_decode<NL>, dim3((unsigned)gb), dim3(256), 0, s, buf, nbytes, nch, L, entry, offs, btot, \
+    hipLaunchKernelGGL((k_nb_decode<NL, G>), dim3((unsigned)gb), dim3(256), 0, s, g, nch, L, entry, offs, btot,    \
                        sync, tmask, key, ts, val, rec_cap, wm_pos, wm_val, wm_cap, d_st)
     if (wide) {
         NB_LAUNCH(GW_MAX_ELEMENT);
@@ -693,6 +741,61 @@ hipError_t launch_nb_decode(const uint8_t* buf, int64_t nbytes, const NbLayout& 
     }
 #undef NB_LAUNCH
     return hipGetLastError();
+}
+
+hipError_t launch_nb_decode(const uint8_t* buf, int64_t nbytes, const NbLayout& L, int64_t* key, int64_t* ts,
+                            int64_t* val, int64_t rec_cap, int64_t* wm_pos, int64_t* wm_val, int64_t wm_cap,
+                            void* scratch, NbStatus* d_st, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(d_st, 0, sizeof(NbStatus), s);
+    if (e != hipSuccess || nbytes <= 0) return e;
+    const int64_t nch = (nbytes + kNbChunk - 1) / kNbChunk;
+    return nb_launch(NbFlat{buf, nbytes}, nch, L, key, ts, val, rec_cap, wm_pos, wm_val, wm_cap, scratch, d_st, s);
+}
+
+// ---- segmented decode ---------------------------------------------------------
+// Chunk descriptors from the range table: chunk c belongs to the last range whose first
+// chunk is <= c (an empty range shares its first chunk with the range after it).
+__global__ void __launch_bounds__(256) k_nb_desc(const NbRange* rt, int32_t nranges, int64_t nch, NbChunkDesc* d) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nch) return;
+    int lo = 0, hi = nranges - 1;  // rt[0].first == 0 <= c
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rt[mid].first <= c) lo = mid; else hi = mid - 1;
+    }
+    const int64_t off = (c - rt[lo].first) * kNbChunk;
+    d[c] = NbChunkDesc{rt[lo].ptr + off, rt[lo].len - off, lo, (int32_t)rt[lo].first};
+}
+
+int64_t nb_seg_plan(NbRange* ranges, int32_t nranges) {
+    int64_t nch = 0;
+    for (int32_t r = 0; r < nranges; ++r) {
+        ranges[r].first = nch;
+        nch += (ranges[r].len + kNbChunk - 1) / kNbChunk;
+    }
+    return nch <= INT32_MAX ? nch : -1;
+}
+
+int64_t nb_seg_scratch_bytes(int64_t nchunks, int32_t nranges) {
+    return nb_scratch_bytes(nchunks * kNbChunk) + nchunks * (int64_t)sizeof(NbChunkDesc) +
+           (int64_t)nranges * (int64_t)sizeof(NbRange);
+}
+
+hipError_t launch_nb_decode_seg(const NbRange* ranges, int32_t nranges, int64_t nchunks, const NbLayout& L,
+                                int64_t* key, int64_t* ts, int64_t* val, int64_t rec_cap, int64_t* ev_pos,
+                                int32_t* ev_kind, int64_t* ev_val, int64_t ev_cap, void* scratch, NbStatus* d_st,
+                                int64_t* d_rng, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(d_st, 0, sizeof(NbStatus), s);
+    if (e == hipSuccess && nranges > 0) e = hipMemsetAsync(d_rng, 0, (size_t)nranges * 24, s);
+    if (e != hipSuccess || nranges <= 0 || nchunks <= 0) return e;
+    NbChunkDesc* desc = (NbChunkDesc*)((uint8_t*)scratch + nb_scratch_bytes(nchunks * kNbChunk));
+    NbRange* d_rt = (NbRange*)(desc + nchunks);
+    e = hipMemcpyAsync(d_rt, ranges, (size_t)nranges * sizeof(NbRange), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_nb_desc, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, s, d_rt, nranges, nchunks,
+                       desc);
+    return nb_launch(NbSeg{desc, d_rng, ev_kind, nranges}, nchunks, L, key, ts, val, rec_cap, ev_pos, ev_val,
+                     ev_cap, scratch, d_st, s);
 }
 
 }  // namespace gw

@@ -10,6 +10,7 @@
 #include <array>
 #include <functional>
 #include <map>
+#include <memory>
 #include <set>
 #include <atomic>
 #include <chrono>
@@ -32,6 +33,7 @@
 #include "gw_session.h"
 #include "gw_snapshot.h"
 #include "gw_sort.h"
+#include "gw_valve.h"
 
 using namespace gw;
 
@@ -236,6 +238,16 @@ struct gw_handle {
     PinnedBuf<uint8_t> h_nbbytes;
     DevBuf<uint8_t> d_nbbytes;
     static constexpr int64_t kNbWmHost = 4096;
+    // several input channels (gw_set_input_channels, gw_ingest_channels*): the valve, the
+    // event list (position | value | kind, nb_ev_cap() each), the per-range results and the
+    // pinned range table of the segmented decode
+    std::unique_ptr<Valve> valve;
+    DevBuf<int64_t> nb_ev;
+    int64_t nb_ev_cap() const { return nb_ev.cap / 3; }
+    PinnedBuf<int64_t> h_nbev;   // 3 * kNbWmHost
+    DevBuf<int64_t> nb_rng;      // consumed | first record | first event, per range
+    PinnedBuf<int64_t> h_nbrng;
+    PinnedBuf<NbRange> h_nbrt;
     bool session = false;
 
     // pane geometry
@@ -3635,6 +3647,9 @@ int gw_decode_serialized(const void* d_bytes, int64_t nbytes, const gw_record_la
     return rc;
 }
 
+static const char kChannelsSet[] =
+    "the handle reads several input channels (gw_set_input_channels): use gw_ingest_channels*";
+
 static int nb_ensure(gw_handle* h, int64_t nbytes, const NbLayout& L) {
     const int64_t want = std::max<int64_t>(nbytes, 1 << 16);
     // upper bounds: every element a record without timestamp / a watermark
@@ -3714,6 +3729,7 @@ static int nb_ingest_on_stream(gw_handle* h, const uint8_t* d_bytes, int64_t nby
 int gw_ingest_serialized_device(gw_handle* h, const void* d_bytes, int64_t nbytes, const gw_record_layout* layout,
                                 void* stream, int64_t* consumed, int64_t* rows_fired) {
     if (!h) return GW_E_INVALID;
+    if (h->valve) return h->fail(GW_E_INVALID, "%s", kChannelsSet);
     if (h->fe) return h->fail(GW_E_UNSUPPORTED, "network-buffer ingest of first-element rows is not supported");
     if (h->cfg.assigner == GW_SESSION_DYNAMIC)
         return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "network-buffer ingest (gw_ingest_serialized*)");
@@ -3751,6 +3767,7 @@ int gw_ingest_serialized_device(gw_handle* h, const void* d_bytes, int64_t nbyte
 int gw_ingest_serialized(gw_handle* h, const void* bytes, int64_t nbytes, const gw_record_layout* layout,
                          int64_t* consumed, int64_t* rows_fired) {
     if (!h) return GW_E_INVALID;
+    if (h->valve) return h->fail(GW_E_INVALID, "%s", kChannelsSet);
     if (h->fe) return h->fail(GW_E_UNSUPPORTED, "network-buffer ingest of first-element rows is not supported");
     if (h->cfg.assigner == GW_SESSION_DYNAMIC)
         return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "network-buffer ingest (gw_ingest_serialized*)");
@@ -3787,6 +3804,364 @@ int gw_ingest_serialized(gw_handle* h, const void* bytes, int64_t nbytes, const 
     hipError_t e = hipMemcpyAsync(h->d_nbbytes, h->h_nbbytes, (size_t)nbytes, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return h->fail(GW_E_DEVICE, "H2D: %s", hipGetErrorString(e));
     return nb_ingest_on_stream(h, h->d_nbbytes, nbytes, L, consumed, rows_fired);
+}
+
+// ---- several input channels: the valve, the segmented decode, the replay ------------
+struct gw_valve {
+    Valve v;
+    explicit gw_valve(int n) : v(n) {}
+};
+
+int gw_valve_create(int32_t nchannels, gw_valve** out) {
+    if (!out) { g_create_error = "null argument"; return GW_E_INVALID; }
+    *out = nullptr;
+    if (nchannels < 1 || nchannels > GW_MAX_INPUT_CHANNELS) {
+        g_create_error = "valve: 1..GW_MAX_INPUT_CHANNELS channels";
+        return GW_E_INVALID;
+    }
+    gw_valve* v = new (std::nothrow) gw_valve(nchannels);
+    if (!v) { g_create_error = "out of host memory"; return GW_E_OOM; }
+    *out = v;
+    return GW_OK;
+}
+
+int gw_valve_destroy(gw_valve* v) {
+    delete v;
+    return GW_OK;
+}
+
+// One event into a valve; why: set on GW_E_INVALID.
+static int valve_feed(Valve& v, int32_t channel, int32_t kind, int64_t value, Valve::Out& o, const char*& why) {
+    if (channel < 0 || channel >= (int32_t)v.ch.size()) { why = "valve: channel out of range"; return GW_E_INVALID; }
+    if (kind == GW_EVENT_WATERMARK) {
+        o = v.watermark(channel, value);
+    } else if (kind == GW_EVENT_STATUS) {
+        if (value != GW_STATUS_ACTIVE && value != GW_STATUS_IDLE) {
+            why = "valve: a watermark status is 0 (active) or -1 (idle)";
+            return GW_E_INVALID;
+        }
+        o = v.status(channel, (int32_t)value);
+    } else {
+        why = "valve: unknown event kind";
+        return GW_E_INVALID;
+    }
+    return GW_OK;
+}
+
+int gw_valve_input(gw_valve* v, int32_t channel, int32_t kind, int64_t value, gw_valve_output* out) {
+    if (!v || !out) { g_create_error = "null argument"; return GW_E_INVALID; }
+    Valve::Out o;
+    const char* why = "";
+    const int rc = valve_feed(v->v, channel, kind, value, o, why);
+    if (rc) { g_create_error = why; return rc; }
+    out->has_watermark = o.has_wm;
+    out->has_status = o.has_status;
+    out->watermark = o.wm;
+    out->status = o.status;
+    out->reserved = 0;
+    return GW_OK;
+}
+
+// The range of the earliest error of a segmented decode and its byte position there (virtual
+// positions order the errors by range, then byte); -1 where the status holds none.
+static int32_t nb_seg_error_at(const NbStatus& st, const NbRange* rt, int32_t nranges, int64_t& pos) {
+    const unsigned long long rank = nb_corrupt_first(st) ? st.corrupt : st.unsupported;
+    pos = 0;
+    if (!rank || nranges <= 0) return -1;
+    const int64_t vpos = (int64_t)((1ull << 62) - rank), chunk = vpos / kNbChunk;
+    int32_t r = nranges - 1;
+    while (r > 0 && rt[r].first > chunk) --r;
+    pos = vpos - rt[r].first * kNbChunk;
+    return r;
+}
+
+static std::string nb_seg_why(const std::string& why, int32_t range, int64_t pos) {
+    if (range < 0) return why;
+    return why + " (range " + std::to_string(range) + ", byte " + std::to_string((long long)pos) + ")";
+}
+
+// Per-range counts from the ranges' first record / event: an empty range has none.
+static void nb_seg_counts(const NbRange* rt, int32_t nranges, const int64_t* first, int64_t total, int64_t* count) {
+    int64_t next = total;
+    for (int32_t r = nranges; r-- > 0;) {
+        if (rt[r].len > 0) {
+            count[r] = next - first[r];
+            next = first[r];
+        } else {
+            count[r] = 0;
+        }
+    }
+}
+
+int gw_decode_channels_device(int32_t nranges, const void* const* d_ptr, const int64_t* len,
+                              const gw_record_layout* layout, int64_t* d_key, int64_t* d_ts, int64_t* d_value,
+                              int64_t rec_cap, int64_t* d_ev_pos, int32_t* d_ev_kind, int64_t* d_ev_val,
+                              int64_t ev_cap, int64_t* consumed, int64_t* rec_count, int64_t* ev_count,
+                              gw_decode_channels_result* out, void* stream) {
+    NbLayout L{};
+    std::string why;
+    int rc = nb_layout(layout, -1, L, why);
+    if (rc) { g_create_error = why; return rc; }
+    if (nranges < 0 || nranges > (1 << 20) || !out || (nranges > 0 && (!d_ptr || !len))) {
+        g_create_error = "bad range list";
+        return GW_E_INVALID;
+    }
+    for (int32_t r = 0; r < nranges; ++r)
+        if (len[r] < 0 || (len[r] > 0 && !d_ptr[r]) || ((uintptr_t)d_ptr[r] & 3)) {
+            g_create_error = "bad byte range " + std::to_string(r) + " (device pointer, 4-byte aligned)";
+            return GW_E_INVALID;
+        }
+    if ((rec_cap > 0 && (!d_key || !d_ts)) || (ev_cap > 0 && (!d_ev_pos || !d_ev_kind || !d_ev_val))) {
+        g_create_error = "null output column";
+        return GW_E_INVALID;
+    }
+    *out = gw_decode_channels_result{};
+    out->error_range = -1;
+    for (int32_t r = 0; r < nranges; ++r) {
+        if (consumed) consumed[r] = 0;
+        if (rec_count) rec_count[r] = 0;
+        if (ev_count) ev_count[r] = 0;
+    }
+    if (nranges == 0) return GW_OK;
+    hipStream_t s = (hipStream_t)stream;
+    // plain host memory (pinning costs more than this call's copies: a few words per range);
+    // it outlives the copies, the stream is synchronised below
+    const int64_t rw = 3 * (int64_t)nranges;
+    std::vector<NbRange> rtv((size_t)nranges);
+    std::vector<int64_t> h_rngv((size_t)rw + (sizeof(NbStatus) + 7) / 8);  // the per-range words, then the status
+    NbRange* rt = rtv.data();
+    int64_t* h_rng = h_rngv.data();
+    NbStatus* hst = (NbStatus*)(h_rng + rw);
+    for (int32_t r = 0; r < nranges; ++r) rt[r] = NbRange{(const uint8_t*)d_ptr[r], len[r], 0};
+    const int64_t nch = nb_seg_plan(rt, nranges);
+    if (nch < 0) { g_create_error = "decode: more than 2^31 chunks"; return GW_E_RANGE; }
+    // one device block: the scratch, then the per-range words and the status
+    const int64_t sb = (nb_seg_scratch_bytes(nch, nranges) + 15) & ~(int64_t)15;
+    DevBuf<char> scratch;
+    hipError_t e = scratch.reserve_discard(sb + rw * 8 + (int64_t)sizeof(NbStatus));
+    int64_t* d_rng = (int64_t*)(scratch.get() + sb);
+    NbStatus* d_st = (NbStatus*)(d_rng + rw);
+    if (e == hipSuccess)
+        e = launch_nb_decode_seg(rt, nranges, nch, L, d_key, d_ts, d_value, rec_cap, d_ev_pos, d_ev_kind, d_ev_val,
+                                 ev_cap, scratch, d_st, d_rng, s);
+    if (e == hipSuccess)  // (contiguous on both sides: one copy)
+        e = hipMemcpyAsync(h_rng, d_rng, (size_t)rw * 8 + sizeof(NbStatus), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { g_create_error = std::string("decode: ") + hipGetErrorString(e); return GW_E_DEVICE; }
+    out->records = hst->records;
+    out->events = hst->watermarks;
+    out->skipped = (int64_t)hst->skipped;
+    if (consumed) std::copy(h_rng, h_rng + nranges, consumed);
+    if (rec_count) nb_seg_counts(rt, nranges, h_rng + nranges, hst->records, rec_count);
+    if (ev_count) nb_seg_counts(rt, nranges, h_rng + 2 * nranges, hst->watermarks, ev_count);
+    rc = nb_status_code(*hst, why);
+    if (rc) {
+        out->error_range = nb_seg_error_at(*hst, rt, nranges, out->error_pos);
+        g_create_error = nb_seg_why(why, out->error_range, out->error_pos);
+    }
+    return rc;
+}
+
+int gw_set_input_channels(gw_handle* h, int32_t n) {
+    if (!h) return GW_E_INVALID;
+    if (h->fe) return h->fail(GW_E_UNSUPPORTED, "network-buffer ingest of first-element rows is not supported");
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "network-buffer ingest (gw_ingest_channels*)");
+    if (n < 1 || n > GW_MAX_INPUT_CHANNELS) return h->fail(GW_E_INVALID, "1..GW_MAX_INPUT_CHANNELS input channels");
+    h->valve.reset(new (std::nothrow) Valve(n));
+    if (!h->valve) return h->fail(GW_E_OOM, "out of host memory");
+    return GW_OK;
+}
+
+int gw_input_status(gw_handle* h, int64_t* watermark, int32_t* idle) {
+    if (!h) return GW_E_INVALID;
+    if (!h->valve) return h->fail(GW_E_STATE, "no input channels set (gw_set_input_channels)");
+    if (watermark) *watermark = h->valve->last_wm;
+    if (idle) *idle = h->valve->idle ? 1 : 0;
+    return GW_OK;
+}
+
+// What both gw_ingest_channels* check before touching the device; total: the bytes of the call.
+static int nb_channels_check(gw_handle* h, int32_t nranges, const int32_t* channel, const void* const* ptr,
+                             const int64_t* len, const gw_record_layout* layout, bool device, NbLayout& L,
+                             int64_t& total) {
+    if (h->fe) return h->fail(GW_E_UNSUPPORTED, "network-buffer ingest of first-element rows is not supported");
+    if (h->cfg.assigner == GW_SESSION_DYNAMIC)
+        return h->fail(GW_E_UNSUPPORTED, kDynUnsupported, "network-buffer ingest (gw_ingest_channels*)");
+    if (!h->valve) return h->fail(GW_E_STATE, "no input channels set (gw_set_input_channels)");
+    if (h->failed) return h->fail(GW_E_STATE, "operator failed earlier: %s", h->err.c_str());
+    std::string why;
+    const int rc = nb_layout(layout, h->cfg.agg, L, why);
+    if (rc) return h->fail(rc, "%s", why.c_str());
+    const int32_t n = (int32_t)h->valve->ch.size();
+    if (nranges < 0 || nranges > n || (nranges > 0 && (!channel || !ptr || !len)))
+        return h->fail(GW_E_INVALID, "bad range list (at most one range per input channel)");
+    std::vector<bool> seen((size_t)n, false);
+    total = 0;
+    for (int32_t r = 0; r < nranges; ++r) {
+        if (channel[r] < 0 || channel[r] >= n)
+            return h->fail(GW_E_INVALID, "range %d: channel %d outside [0, %d)", r, channel[r], n);
+        if (seen[(size_t)channel[r]]) return h->fail(GW_E_INVALID, "channel %d appears twice in one call", channel[r]);
+        seen[(size_t)channel[r]] = true;
+        if (len[r] < 0 || (len[r] > 0 && !ptr[r]) || (device && ((uintptr_t)ptr[r] & 3)))
+            return h->fail(GW_E_INVALID, "range %d: bad byte buffer%s", r, device ? " (device pointer, 4-byte aligned)" : "");
+        total += len[r];
+    }
+    return GW_OK;
+}
+
+// Segmented decode of the ranges in h->h_nbrt on the handle's stream, then the replay: every
+// event through the valve; the records before a watermark the valve emits as one batch, then
+// the watermark.
+static int nb_channels_on_stream(gw_handle* h, int32_t nranges, const int32_t* channel, int64_t total,
+                                 const NbLayout& L, int64_t* consumed, int64_t* rows_fired) {
+    NbRange* rt = h->h_nbrt;
+    const int64_t nch = nb_seg_plan(rt, nranges);
+    if (nch < 0) return h->fail(GW_E_RANGE, "more than 2^31 chunks in one call");
+    // upper bounds: every element a record without timestamp / a watermark status
+    const int64_t want = std::max<int64_t>(total, 1 << 16), rw = 3 * (int64_t)nranges;
+    const int64_t recs = want / (4 + 1 + L.vbytes) + 1, evs = want / 9 + 1;
+    hipError_t e = h->nb_scratch.reserve_discard(nb_seg_scratch_bytes(want / kNbChunk + nranges + 1, nranges));
+    if (e == hipSuccess) e = h->nb_cols.reserve_discard(3 * recs);
+    if (e == hipSuccess) e = h->nb_ev.reserve_discard(3 * evs);
+    if (e == hipSuccess) e = h->nb_rng.reserve_discard(rw);
+    if (e == hipSuccess) e = h->d_nbst.reserve_discard(1);
+    if (e == hipSuccess && !h->h_nbst) e = h->h_nbst.alloc(1, hipHostMallocDefault);
+    if (e == hipSuccess && !h->h_nbev) e = h->h_nbev.alloc(3 * gw_handle::kNbWmHost, hipHostMallocDefault);
+    if (e == hipSuccess && h->h_nbrng.cap < rw) e = h->h_nbrng.alloc(rw, hipHostMallocDefault);
+    if (e != hipSuccess) return h->fail(GW_E_OOM, "network-buffer scratch: %s", hipGetErrorString(e));
+    const int64_t rcap = h->nb_rec_cap(), ecap = h->nb_ev_cap(), kH = gw_handle::kNbWmHost;
+    int64_t* k = h->nb_cols;
+    int64_t* t = k + rcap;
+    int64_t* v = k + 2 * rcap;
+    int64_t* ep = h->nb_ev;
+    int64_t* ev = ep + ecap;
+    int32_t* ek = (int32_t*)(ep + 2 * ecap);
+    e = launch_nb_decode_seg(rt, nranges, nch, L, k, t, L.val_type ? v : nullptr, rcap, ep, ek, ev, ecap,
+                             h->nb_scratch, h->d_nbst, h->nb_rng, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbst, h->d_nbst, sizeof(NbStatus), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbrng, h->nb_rng, (size_t)rw * 8, hipMemcpyDeviceToHost, h->stream);
+    const int64_t pre = std::min(kH, ecap);  // the first events come with the status
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbev, ep, (size_t)pre * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbev + kH, ev, (size_t)pre * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->h_nbev + 2 * kH, ek, (size_t)pre * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return h->fail(GW_E_DEVICE, "network-buffer decode: %s", hipGetErrorString(e));
+    const NbStatus st = *h->h_nbst;
+    std::string why;
+    int rc = nb_status_code(st, why);
+    if (rc) {
+        int64_t pos = 0;
+        const int32_t r = nb_seg_error_at(st, rt, nranges, pos);
+        h->fail(rc, "%s", nb_seg_why(why, r, pos).c_str());
+        if (rc == GW_E_INVALID) h->failed = true;  // IOException: the task fails
+        return rc;
+    }
+    const int64_t ne = st.watermarks;
+    std::vector<int64_t> epos((size_t)ne), eval((size_t)ne), ecnt((size_t)nranges);
+    std::vector<int32_t> ekind((size_t)ne);
+    if (ne > pre) {
+        e = hipMemcpy(epos.data(), ep, (size_t)ne * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(eval.data(), ev, (size_t)ne * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(ekind.data(), ek, (size_t)ne * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return h->fail(GW_E_DEVICE, "event list: %s", hipGetErrorString(e));
+    } else {
+        std::copy(h->h_nbev.p, h->h_nbev.p + ne, epos.begin());
+        std::copy(h->h_nbev.p + kH, h->h_nbev.p + kH + ne, eval.begin());
+        const int32_t* hk = (const int32_t*)(h->h_nbev.p + 2 * kH);
+        std::copy(hk, hk + ne, ekind.begin());
+    }
+    nb_seg_counts(rt, nranges, h->h_nbrng + 2 * nranges, ne, ecnt.data());
+    if (consumed) std::copy(h->h_nbrng.p, h->h_nbrng.p + nranges, consumed);
+    const bool leaf = h->kids.empty();
+    auto ingest = [&](int64_t from, int64_t upto) -> int {
+        if (upto <= from) return GW_OK;
+        const int64_t* vv = L.val_type ? v + from : nullptr;
+        return leaf ? ingest_device_impl(h, upto - from, k + from, t + from, vv)
+                    : gw_ingest_device(h, upto - from, k + from, nullptr, t + from, vv, h->stream);
+    };
+    int64_t fired = 0, done = 0, i = 0;
+    for (int32_t r = 0; r < nranges; ++r) {
+        for (const int64_t end = i + ecnt[(size_t)r]; i < end; ++i) {
+            Valve::Out o;
+            const char* bad = "";
+            rc = valve_feed(*h->valve, channel[r], ekind[(size_t)i], eval[(size_t)i], o, bad);
+            if (rc) {
+                h->failed = true;  // a status the serializer cannot have written: the stream is corrupt
+                return h->fail(rc, "%s (range %d)", bad, r);
+            }
+            if (!o.has_wm) continue;
+            rc = ingest(done, epos[(size_t)i]);
+            if (rc) return rc;
+            done = std::max(done, epos[(size_t)i]);
+            int64_t f = 0;
+            rc = gw_advance_watermark(h, o.wm, &f);
+            if (rc) return rc;
+            fired += f;
+        }
+    }
+    rc = ingest(done, st.records);
+    if (rc) return rc;
+    if (rows_fired) *rows_fired = fired;
+    return GW_OK;
+}
+
+int gw_ingest_channels_device(gw_handle* h, int32_t nranges, const int32_t* channel, const void* const* d_ptr,
+                              const int64_t* len, const gw_record_layout* layout, void* stream, int64_t* consumed,
+                              int64_t* rows_fired) {
+    if (!h) return GW_E_INVALID;
+    NbLayout L{};
+    int64_t total = 0;
+    int rc = nb_channels_check(h, nranges, channel, d_ptr, len, layout, true, L, total);
+    if (rc) return rc;
+    if (rows_fired) *rows_fired = 0;
+    for (int32_t r = 0; r < nranges && consumed; ++r) consumed[r] = 0;
+    if (total == 0) return GW_OK;
+    hipSetDevice(h->cfg.device);
+    if (h->h_nbrt.cap < nranges && h->h_nbrt.alloc(std::max<int64_t>(nranges, 64), hipHostMallocDefault) != hipSuccess)
+        return h->fail(GW_E_OOM, "range table");
+    for (int32_t r = 0; r < nranges; ++r) h->h_nbrt[r] = NbRange{(const uint8_t*)d_ptr[r], len[r], 0};
+    hipStream_t ps = (hipStream_t)stream;
+    if (ps != h->stream) {
+        hipEventRecord(h->ev_in, ps);
+        hipStreamWaitEvent(h->stream, h->ev_in, 0);
+    }
+    // the decode has read the bytes once this returns (it synchronises the handle's stream)
+    return nb_channels_on_stream(h, nranges, channel, total, L, consumed, rows_fired);
+}
+
+int gw_ingest_channels(gw_handle* h, int32_t nranges, const int32_t* channel, const void* const* ptr,
+                       const int64_t* len, const gw_record_layout* layout, int64_t* consumed, int64_t* rows_fired) {
+    if (!h) return GW_E_INVALID;
+    NbLayout L{};
+    int64_t total = 0;
+    int rc = nb_channels_check(h, nranges, channel, ptr, len, layout, false, L, total);
+    if (rc) return rc;
+    if (rows_fired) *rows_fired = 0;
+    for (int32_t r = 0; r < nranges && consumed; ++r) consumed[r] = 0;
+    if (total == 0) return GW_OK;
+    hipSetDevice(h->cfg.device);
+    if (h->h_nbrt.cap < nranges && h->h_nbrt.alloc(std::max<int64_t>(nranges, 64), hipHostMallocDefault) != hipSuccess)
+        return h->fail(GW_E_OOM, "range table");
+    // every range at a 16-byte offset of one staging buffer: one copy to the device
+    const int64_t staged = total + 16 * (int64_t)nranges;
+    if (staged > h->d_nbbytes.cap) {  // (the device buffer is the last to be allocated)
+        const int64_t cap = std::max<int64_t>(staged, 1 << 20);
+        h->d_nbbytes.reset();
+        hipError_t e = h->h_nbbytes.alloc(cap, hipHostMallocDefault);
+        if (e == hipSuccess) e = h->d_nbbytes.reserve_discard(cap);
+        if (e != hipSuccess) return h->fail(GW_E_OOM, "network-buffer staging: %s", hipGetErrorString(e));
+    }
+    // the previous call synchronised the stream, so the pinned staging is free
+    int64_t off = 0;
+    for (int32_t r = 0; r < nranges; ++r) {
+        if (len[r] > 0) memcpy(h->h_nbbytes + off, ptr[r], (size_t)len[r]);
+        h->h_nbrt[r] = NbRange{h->d_nbbytes + off, len[r], 0};
+        off = (off + len[r] + 15) & ~(int64_t)15;
+    }
+    hipError_t e = hipMemcpyAsync(h->d_nbbytes, h->h_nbbytes, (size_t)off, hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) return h->fail(GW_E_DEVICE, "H2D: %s", hipGetErrorString(e));
+    return nb_channels_on_stream(h, nranges, channel, total, L, consumed, rows_fired);
 }
 
 int gw_advance_watermark(gw_handle* h, int64_t wm, int64_t* rows_fired) {
@@ -4180,7 +4555,9 @@ static int restore_any(gw_handle* h, const void* buf, int64_t len, bool dry) {
 
 int gw_restore(gw_handle* h, const void* buf, int64_t len) {
     if (!h) return GW_E_INVALID;
-    return restore_any(h, buf, len, false);
+    const int rc = restore_any(h, buf, len, false);
+    if (rc == GW_OK && h->valve) h->valve->reset();  // like the watermark, not part of the state
+    return rc;
 }
 
 // The blob layout is snap::Header (96 bytes: kg_lo at 60, kg_hi at 64, reserved at 68,

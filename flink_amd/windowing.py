@@ -330,6 +330,51 @@ def top_n_host(key, start, end, result, top: int, smallest: bool = False, f64: b
 
 
 # ------------------------------------------------------------------------ operator
+class StatusWatermarkValve:
+    """The valve of an input gate with n channels (gw_valve; host code, no device): feed it each
+    channel's watermarks and watermark statuses, act on what it emits.  Every input returns a
+    list of at most two emissions, ("watermark", t) before ("status", idle)."""
+
+    def __init__(self, n: int):
+        v = ctypes.c_void_p()
+        rc = N.lib().gw_valve_create(int(n), ctypes.byref(v))
+        if rc == N.GW_E_INVALID:
+            raise ValueError(N.lib().gw_last_error(None).decode())
+        N.check(rc)
+        self._v, self.n = v, int(n)
+
+    def _input(self, channel: int, kind: int, value: int) -> list:
+        o = N.GwValveOutput()
+        N.check(N.lib().gw_valve_input(self._v, int(channel), kind, int(value), ctypes.byref(o)))
+        out = []
+        if o.has_watermark:
+            out.append(("watermark", o.watermark))
+        if o.has_status:
+            out.append(("status", o.status == N.STATUS_IDLE))
+        return out
+
+    def input_watermark(self, channel: int, timestamp: int) -> list:
+        return self._input(channel, N.EVENT_WATERMARK, timestamp)
+
+    def input_status(self, channel: int, idle: bool) -> list:
+        return self._input(channel, N.EVENT_STATUS, N.STATUS_IDLE if idle else N.STATUS_ACTIVE)
+
+    def input_event(self, channel: int, kind: int, value: int) -> list:
+        """kind / value as the decoder writes them (N.EVENT_*; a status value as serialized)."""
+        return self._input(channel, kind, value)
+
+    def close(self):
+        if self._v:
+            N.lib().gw_valve_destroy(self._v)
+            self._v = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GpuWindowOperator:
     """Keyed event-time window operator on one MI355X (one Flink subtask).
 
@@ -653,6 +698,73 @@ class GpuWindowOperator:
         if carry:
             raise N.GpuWinError(-1, f"{len(carry)} bytes of an incomplete element at the end of the input")
         return fired
+
+    # several input channels (gw_set_input_channels, gw_ingest_channels*) -----------------------
+    def set_input_channels(self, n: int):
+        """The operator reads n input channels through a StatusWatermarkValve of its own: what it
+        acts on is the minimum watermark over the active, aligned channels."""
+        self._ensure_handle()
+        N.check(N.lib().gw_set_input_channels(self._h, int(n)), self._h)
+        self._channel_carry = {}
+        return self
+
+    def process_channels(self, parts, layout: "N.GwRecordLayout") -> tuple:
+        """parts: [(channel, bytes)], each channel at most once; processed as if the parts had
+        arrived in list order (gw_ingest_channels: one decode, one synchronisation).  Returns
+        (consumed per part, rows_fired)."""
+        self._ensure_handle()
+        n = len(parts)
+        chan = (ctypes.c_int32 * max(n, 1))(*[int(c) for c, _ in parts])
+        bufs = [ctypes.create_string_buffer(bytes(d), len(d)) if len(d) else None for _, d in parts]
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) if b is not None else None
+                                               for b in bufs])
+        lens = (ctypes.c_int64 * max(n, 1))(*[len(d) for _, d in parts])
+        consumed = (ctypes.c_int64 * max(n, 1))()
+        fired = ctypes.c_int64(0)
+        N.check(N.lib().gw_ingest_channels(self._h, n, chan, ptrs, lens, ctypes.byref(layout), consumed,
+                                           ctypes.byref(fired)), self._h)
+        return list(consumed)[:n], fired.value
+
+    def process_channels_device(self, parts, layout: "N.GwRecordLayout", stream=None) -> tuple:
+        """Same, with each part's bytes in a device uint8 tensor (4-byte aligned; separate
+        allocations allowed), produced on `stream`."""
+        self._ensure_handle()
+        n = len(parts)
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        chan = (ctypes.c_int32 * max(n, 1))(*[int(c) for c, _ in parts])
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() if t.numel() else None for _, t in parts])
+        lens = (ctypes.c_int64 * max(n, 1))(*[t.numel() for _, t in parts])
+        consumed = (ctypes.c_int64 * max(n, 1))()
+        fired = ctypes.c_int64(0)
+        N.check(N.lib().gw_ingest_channels_device(self._h, n, chan, ptrs, lens, ctypes.byref(layout),
+                                                  ctypes.c_void_p(stream) if stream else None, consumed,
+                                                  ctypes.byref(fired)), self._h)
+        return list(consumed)[:n], fired.value
+
+    def process_channel_buffers(self, parts, layout: "N.GwRecordLayout") -> int:
+        """One poll of the input gate: parts = [(channel, bytes)] as process_channels takes them.
+        Each channel's unconsumed tail (an element spanning into its next buffer) is kept and
+        prepended to the channel's next bytes, as process_buffers does for one channel.  Returns
+        the rows fired."""
+        carry = self._channel_carry = getattr(self, "_channel_carry", None) or {}
+        data = [(c, carry.get(c, b"") + bytes(d)) for c, d in parts]
+        used, fired = self.process_channels(data, layout)
+        for (c, d), u in zip(data, used):
+            carry[c] = d[u:]
+        return fired
+
+    def channel_tails(self) -> dict:
+        """Bytes of incomplete elements waiting per channel (process_channel_buffers)."""
+        return {c: len(t) for c, t in (getattr(self, "_channel_carry", None) or {}).items() if t}
+
+    def input_status(self) -> tuple:
+        """(watermark, idle): the last output of the handle's valve (gw_input_status), which the
+        operator forwards downstream."""
+        wm, idle = ctypes.c_int64(0), ctypes.c_int32(0)
+        N.check(N.lib().gw_input_status(self._h, ctypes.byref(wm), ctypes.byref(idle)), self._h)
+        return wm.value, bool(idle.value)
 
     # staged host ingest (gw_stage_*): pinned library-owned columns filled in place ------------
     def stage_alloc(self, slots: int, cap: int):

@@ -360,6 +360,90 @@ int  gw_ingest_serialized_device(gw_handle* h, const void* d_bytes, int64_t nbyt
                                  const gw_record_layout* layout, void* stream, int64_t* consumed,
                                  int64_t* rows_fired);
 
+/* ---- several input channels ---------------------------------------------------
+ * An operator behind a keyBy reads one input channel per upstream subtask and acts on the
+ * output of StatusWatermarkValve: the minimum watermark over the channels that are active
+ * and aligned.  gw_valve is that valve by itself (host code, no device); a handle with
+ * gw_set_input_channels owns one and gw_ingest_channels* feeds it. */
+#define GW_EVENT_WATERMARK 0   /* value: the watermark's timestamp                        */
+#define GW_EVENT_STATUS    1   /* value: GW_STATUS_ACTIVE / GW_STATUS_IDLE (WatermarkStatus) */
+#define GW_STATUS_ACTIVE   0
+#define GW_STATUS_IDLE   (-1)
+#define GW_MAX_INPUT_CHANNELS 1024
+typedef struct gw_valve gw_valve;
+typedef struct gw_valve_output {
+    int32_t has_watermark;  /* the input emitted a watermark (before the status, if both)  */
+    int32_t has_status;     /* the input emitted a status                                  */
+    int64_t watermark;
+    int32_t status;         /* GW_STATUS_ACTIVE / GW_STATUS_IDLE                           */
+    int32_t reserved;
+} gw_valve_output;
+/* 1 <= nchannels <= GW_MAX_INPUT_CHANNELS.  Every channel starts active and aligned at
+ * Long.MIN_VALUE, the valve's output at Long.MIN_VALUE and ACTIVE. */
+int  gw_valve_create(int32_t nchannels, gw_valve** out);
+int  gw_valve_destroy(gw_valve* v);
+/* One watermark or status of `channel`; *out what it emitted (at most one watermark and one
+ * status).  A watermark is ignored unless the valve's output and the channel are active and
+ * it advances the channel; an idle channel leaves the minimum, and comes back aligned only
+ * once its watermark has caught up with the output; when the last active channel goes idle
+ * the valve flushes the maximum over all channels (if that channel was holding it back) and
+ * emits IDLE.  GW_E_INVALID: channel outside [0, n), unknown kind, a status other than
+ * GW_STATUS_ACTIVE / GW_STATUS_IDLE. */
+int  gw_valve_input(gw_valve* v, int32_t channel, int32_t kind, int64_t value, gw_valve_output* out);
+
+/* Result of gw_decode_channels_device. */
+typedef struct gw_decode_channels_result {
+    int64_t records;      /* over all ranges                                               */
+    int64_t events;       /* watermarks and watermark statuses over all ranges             */
+    int64_t skipped;      /* latency markers and record attributes                         */
+    int32_t error_range;  /* the range of the reported error, -1 if none                   */
+    int32_t reserved;
+    int64_t error_pos;    /* its byte position in that range (chunk-granular for a bad tag) */
+} gw_decode_channels_result;
+/* gw_decode_serialized for nranges byte ranges at once (one per input channel, for example):
+ * one pipeline run whose kernel launches and single host synchronisation do not depend on
+ * nranges.  d_ptr[r] (host array of device pointers, 4-byte aligned, separate allocations
+ * allowed) and len[r] >= 0 give range r.  Every range is a stream of its own: its chain
+ * starts at its first byte, nothing past its end is read, and it may end inside an element
+ * (consumed[r] = end of its last complete element).  Records go to the columns in range
+ * order and stream order within a range, rec_count[r] of them; watermarks (kind
+ * GW_EVENT_WATERMARK) and WatermarkStatus elements (GW_EVENT_STATUS, value as written) to
+ * (ev_pos = records of the whole call before the event, ev_kind, ev_val), ev_count[r] of
+ * them.  consumed, rec_count, ev_count: host arrays of nranges (each may be NULL).  Errors
+ * as gw_decode_serialized; the earliest in (range, byte position) is reported and
+ * gw_last_error(NULL) names the range. */
+int  gw_decode_channels_device(int32_t nranges, const void* const* d_ptr, const int64_t* len,
+                               const gw_record_layout* layout, int64_t* d_key, int64_t* d_ts,
+                               int64_t* d_value, int64_t rec_cap, int64_t* d_ev_pos, int32_t* d_ev_kind,
+                               int64_t* d_ev_val, int64_t ev_cap, int64_t* consumed, int64_t* rec_count,
+                               int64_t* ev_count, gw_decode_channels_result* out, void* stream);
+
+/* The handle reads n input channels (1..GW_MAX_INPUT_CHANNELS) through a valve of its own;
+ * calling it again resets the valve.  From then on gw_ingest_serialized* returns
+ * GW_E_INVALID on this handle: its single-channel valve would bypass this one. */
+int  gw_set_input_channels(gw_handle* h, int32_t n);
+/* Decode and process the bytes of several input channels: range r holds bytes of channel
+ * channel[r] (each channel at most once per call, in [0, n)).  The elements are processed as
+ * if the ranges had arrived in array order: one segmented decode, the watermarks and statuses
+ * go through the handle's valve on the host, the records between two watermarks the valve
+ * emits go through gw_ingest_device's path as one batch, each emitted watermark through
+ * gw_advance_watermark's.  Records are never filtered by status.  consumed[r] (may be NULL)
+ * as in gw_decode_result: the caller keeps each channel's tail.  One host synchronisation
+ * per call.  A window-class composite decodes once for all its children.  First-element and
+ * GW_SESSION_DYNAMIC handles: GW_E_UNSUPPORTED.  A corrupt stream fails the operator. */
+int  gw_ingest_channels_device(gw_handle* h, int32_t nranges, const int32_t* channel, const void* const* d_ptr,
+                               const int64_t* len, const gw_record_layout* layout, void* stream,
+                               int64_t* consumed, int64_t* rows_fired);
+/* Same with the bytes in host memory: the ranges are staged into one pinned buffer at
+ * aligned offsets and copied to the device at once. */
+int  gw_ingest_channels(gw_handle* h, int32_t nranges, const int32_t* channel, const void* const* ptr,
+                        const int64_t* len, const gw_record_layout* layout, int64_t* consumed,
+                        int64_t* rows_fired);
+/* The valve's last output: the watermark it emitted last (Long.MIN_VALUE before the first)
+ * and whether its status is idle -- what the operator forwards downstream.  gw_restore
+ * resets the valve: like the watermark it is not part of the state. */
+int  gw_input_status(gw_handle* h, int64_t* watermark, int32_t* idle);
+
 /* Bounded input ended (BoundedOneInput.endInput) — equivalent to MAX_WATERMARK. */
 int  gw_end_input(gw_handle* h, int64_t* rows_fired);
 

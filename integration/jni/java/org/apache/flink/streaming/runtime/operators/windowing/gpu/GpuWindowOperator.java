@@ -171,6 +171,70 @@ public class GpuWindowOperator<IN, K>
         }
     }
 
+    // Several input channels (setInputChannels): each channel's unconsumed tail and the staging buffer
+    private byte[][] channelTail;
+    private ByteBuffer channelBytes;
+
+    /**
+     * The operator reads {@code n} input channels through a StatusWatermarkValve of its own
+     * (gw_set_input_channels): it acts on the minimum watermark over the active, aligned channels,
+     * idle channels (WatermarkStatus.IDLE) do not hold it back.  From then on the task feeds it with
+     * {@link #ingestChannels}.
+     */
+    public void setInputChannels(int n) {
+        nativeSetInputChannels(handle, n);
+        channelTail = new byte[n][];
+    }
+
+    /**
+     * One poll of the input gate: {@code buffers[r]} holds serialized stream elements of channel
+     * {@code channels[r]} (each channel at most once), processed as if they had arrived in array
+     * order: one decode on the device, the watermarks and statuses through the valve, the records
+     * between two emitted watermarks as one batch (gw_ingest_channels).  The bytes of an element
+     * that spans into the channel's next buffer are kept and prepended to it.  Returns the rows
+     * fired; they are drained as usual.
+     */
+    public long ingestChannels(int[] channels, ByteBuffer[] buffers, String types, int keyField, int valueField) {
+        final int n = channels.length;
+        final long[] offsets = new long[n], lengths = new long[n], consumed = new long[n];
+        long total = 0;
+        for (int r = 0; r < n; r++) {
+            final byte[] tail = channelTail[channels[r]];
+            offsets[r] = total;
+            lengths[r] = (tail == null ? 0 : tail.length) + buffers[r].remaining();
+            total = (total + lengths[r] + 15) & ~15L;  // every range 16-byte aligned
+        }
+        if (total > Integer.MAX_VALUE) throw new IllegalStateException("one poll exceeds one direct buffer");
+        if (channelBytes == null || channelBytes.capacity() < total)
+            channelBytes = ByteBuffer.allocateDirect((int) Math.max(total, 1 << 16));
+        for (int r = 0; r < n; r++) {
+            final byte[] tail = channelTail[channels[r]];
+            channelBytes.position((int) offsets[r]);
+            if (tail != null) channelBytes.put(tail);
+            channelBytes.put(buffers[r].duplicate());
+        }
+        final long rows = nativeIngestChannels(handle, channelBytes, channels, offsets, lengths, consumed, types,
+                keyField, valueField);
+        for (int r = 0; r < n; r++) {
+            final int rest = (int) (lengths[r] - consumed[r]);
+            byte[] tail = null;
+            if (rest > 0) {
+                tail = new byte[rest];
+                channelBytes.position((int) (offsets[r] + consumed[r]));
+                channelBytes.get(tail);
+            }
+            channelTail[channels[r]] = tail;
+        }
+        return rows;
+    }
+
+    /** The valve's last output: {watermark, idle ? 1 : 0}; the operator forwards the status downstream. */
+    public long[] inputStatus() {
+        final long[] out = new long[2];
+        nativeInputStatus(handle, out);
+        return out;
+    }
+
     // gw_assigner / gw_trigger / gw_agg codes of include/gpuwin.h
     private static final int GW_SESSION = 2, GW_COUNT_TUMBLING = 3, GW_COUNT_SLIDING = 4, GW_SESSION_DYNAMIC = 5;
     private int assigner;
@@ -844,6 +908,12 @@ public class GpuWindowOperator<IN, K>
                                                      int channels, int maxParallelism, long watermark,
                                                      java.nio.LongBuffer ranges);
     private static native int nativeDrainLate(long h, ByteBuffer key, ByteBuffer ts, ByteBuffer value, int cap);
+    private static native void nativeSetInputChannels(long h, int n);
+    private static native void nativeInputStatus(long h, long[] out);
+    /** gw_ingest_channels over ranges of one direct buffer; consumed[r] is written; returns the rows fired. */
+    private static native long nativeIngestChannels(long h, ByteBuffer bytes, int[] channels, long[] offsets,
+                                                    long[] lengths, long[] consumed, String types, int keyField,
+                                                    int valueField);
     /** The keyBy exchange's receive columns (GpuKeyByExchange.batch, produced on `stream`)
      *  straight into the operator. */
     static native void nativeIngestDevice(long h, long n, long keyPtr, long hashPtr, long tsPtr, long valuePtr,

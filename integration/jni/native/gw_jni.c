@@ -127,6 +127,84 @@ JNIEXPORT jlong JNICALL CLS(nativeIngestSerialized)(JNIEnv* env, jclass c, jlong
     return consumed;
 }
 
+/* Several input channels: the operator gets a StatusWatermarkValve of its own over n channels
+ * (gw_set_input_channels); from then on it is fed through nativeIngestChannels. */
+JNIEXPORT void JNICALL CLS(nativeSetInputChannels)(JNIEnv* env, jclass c, jlong h, jint n) {
+    fail(env, (gw_handle*)(intptr_t)h, gw_set_input_channels((gw_handle*)(intptr_t)h, n));
+}
+
+/* The valve's last output: out[0] = the watermark, out[1] = 1 if its status is idle. */
+JNIEXPORT void JNICALL CLS(nativeInputStatus)(JNIEnv* env, jclass c, jlong h, jlongArray out) {
+    int64_t wm = 0;
+    int32_t idle = 0;
+    if (fail(env, (gw_handle*)(intptr_t)h, gw_input_status((gw_handle*)(intptr_t)h, &wm, &idle)) < 0) return;
+    const jlong v[2] = {wm, idle};
+    (*env)->SetLongArrayRegion(env, out, 0, 2, v);
+}
+
+/* One poll of the input gate (gw_ingest_channels): `bytes` is a direct ByteBuffer holding the
+ * serialized elements of several channels, range r = [offsets[r], offsets[r] + lengths[r]) the
+ * bytes of channel channels[r] (each channel at most once; its carried tail first).  consumed[r]
+ * receives the bytes of range r that were complete elements; the caller keeps each channel's
+ * rest.  Returns the rows fired.  Reads an int[]: left out under the test-only jni.h of
+ * tests/jni/, compiled by the header of tests/jni/rowenc/. */
+#ifndef GW_TEST_JNI_H
+JNIEXPORT jlong JNICALL CLS(nativeIngestChannels)(JNIEnv* env, jclass c, jlong h, jobject bytes, jintArray channels,
+                                                  jlongArray offsets, jlongArray lengths, jlongArray consumed,
+                                                  jstring types, jint keyField, jint valueField) {
+    gw_handle* g = (gw_handle*)(intptr_t)h;
+    gw_record_layout lay;
+    memset(&lay, 0, sizeof(lay));
+    const char* t = (*env)->GetStringUTFChars(env, types, 0);
+    lay.nfields = (int32_t)strlen(t);
+    if (lay.nfields > GW_MAX_FIELDS) lay.nfields = GW_MAX_FIELDS + 1; /* rejected by gw_ingest_channels */
+    memcpy(lay.types, t, lay.nfields <= GW_MAX_FIELDS ? (size_t)lay.nfields : 0);
+    (*env)->ReleaseStringUTFChars(env, types, t);
+    lay.key_field = keyField;
+    lay.value_field = valueField;
+    const jsize n = (*env)->GetArrayLength(env, channels);
+    if (n < 0 || n > GW_MAX_INPUT_CHANNELS || (*env)->GetArrayLength(env, offsets) != n ||
+        (*env)->GetArrayLength(env, lengths) != n || (*env)->GetArrayLength(env, consumed) != n) {
+        jclass ex = (*env)->FindClass(env, "java/lang/IllegalArgumentException");
+        (*env)->ThrowNew(env, ex, "nativeIngestChannels: channels, offsets, lengths and consumed of one length");
+        return 0;
+    }
+    jint* ch = malloc(sizeof(jint) * (size_t)(n + 1));
+    const void** ptr = malloc(sizeof(void*) * (size_t)(n + 1));
+    int64_t* len = malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t* used = malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t rows = 0;
+    int rc = GW_E_OOM;
+    const int ok = ch && ptr && len && used;
+    if (ok) {
+        const char* base = (*env)->GetDirectBufferAddress(env, bytes);
+        jlong* off = (*env)->GetLongArrayElements(env, offsets, 0);
+        jlong* ln = (*env)->GetLongArrayElements(env, lengths, 0);
+        (*env)->GetIntArrayRegion(env, channels, 0, n, ch);
+        for (jsize r = 0; r < n; ++r) {
+            ptr[r] = base + off[r];
+            len[r] = ln[r];
+            used[r] = 0;
+        }
+        (*env)->ReleaseLongArrayElements(env, lengths, ln, JNI_ABORT);
+        (*env)->ReleaseLongArrayElements(env, offsets, off, JNI_ABORT);
+        rc = gw_ingest_channels(g, n, (const int32_t*)ch, ptr, len, &lay, used, &rows);
+        if (rc >= 0) (*env)->SetLongArrayRegion(env, consumed, 0, n, (const jlong*)used);
+    }
+    free(ch);
+    free(ptr);
+    free(len);
+    free(used);
+    if (!ok) {
+        jclass ex = (*env)->FindClass(env, "java/lang/RuntimeException");
+        (*env)->ThrowNew(env, ex, "nativeIngestChannels: out of memory");
+        return 0;
+    }
+    fail(env, g, rc);
+    return rows;
+}
+#endif
+
 JNIEXPORT jlong JNICALL CLS(nativeAdvanceWatermark)(JNIEnv* env, jclass c, jlong h, jlong wm) {
     int64_t rows = 0;
     fail(env, (gw_handle*)(intptr_t)h, gw_advance_watermark((gw_handle*)(intptr_t)h, wm, &rows));
