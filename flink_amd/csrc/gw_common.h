@@ -211,4 +211,76 @@ GW_HD uint64_t udiv64(uint64_t n, const UDiv64& d) {
     return (t + ((n - t) >> 1)) >> d.shift;
 }
 
+// The same method in 32 bits, for dividends known to be below 2^32 (pass 1 of the region
+// ingest divides ts - t_late, which is for every record a job meets in practice): one
+// multiply-high, and the two shifts of the method's general form (s1 = min(l, 1),
+// s2 = max(l - 1, 0)) instead of a mode, so divisor 1 (magic 1, no shifts: t = 0, q = n) and
+// divisors >= 2^32 (magic 0, shifts 1 and 31: q = 0) take the same five instructions.
+struct UDiv32 {
+    uint32_t magic;
+    uint32_t s1;
+    uint32_t s2;
+};
+GW_HD UDiv32 make_udiv32(uint64_t d) {  // d >= 1
+    UDiv32 r{};
+    if (d >> 32) { r.magic = 0; r.s1 = 1; r.s2 = 31; return r; }
+    uint32_t l = 0;
+    while (((uint64_t)1 << l) < d) ++l;  // l = ceil(log2 d) <= 32
+    r.magic = (uint32_t)(((((uint64_t)1 << l) - d) << 32) / d + 1);
+    r.s1 = l < 1 ? l : 1;
+    r.s2 = l > 1 ? l - 1 : 0;
+    return r;
+}
+GW_HD uint32_t udiv32(uint32_t n, const UDiv32& d) {
+    const uint32_t t = (uint32_t)(((uint64_t)d.magic * n) >> 32);
+    return (t + ((n - t) >> d.s1)) >> d.s2;
+}
+
+// ---------------------------------------------------------------------------
+// Pass 1 of the region ingest (gw_pane.hip k_rgn_p1_lean): the scalars its unrolled loop
+// needs, in one block small enough to stay in scalar registers (IngestArgs is several times
+// the scalar file), and the classification of the common records from them alone.
+// ---------------------------------------------------------------------------
+constexpr int64_t kNarKeyLimit = (1ll << 32) - 2, kNarCountKeyLimit = 1ll << 28, kNarValLimit = 1ll << 27;
+struct P1Hot {
+    const int64_t* key;
+    const int64_t* ts;
+    const int64_t* val;   // nullptr: no values (COUNT)
+    void* out;            // the batch's first buffer tile (records of IngestArgs::p1_key)
+    int64_t n;
+    int64_t t_late;       // IngestArgs::t_late
+    UDiv32 div;           // division by the pane width
+    uint32_t delta;       // IngestArgs::delta, q_refire, t.ring and b_pos: the host takes this
+    uint32_t q_refire;    //   path only when they fit (p1hot_fits)
+    uint32_t ring;
+    uint32_t b_pos;
+    uint32_t bk_sh;       // 31 - pass-1 bucket bits: bucket = (hash >> 33) >> bk_sh
+    uint32_t hmask;       // compact records: the hash's high word without its bucket bits
+    uint32_t late_plain;  // a record below t_late is counted and dropped, nothing else
+};
+// What the lean classification decides: a ring position (>= 0), a late record that is only
+// counted, or "special" -- anything else, which the full classify of the rare pass handles.
+enum { P1_SPECIAL = -1, P1_LATE = -2 };
+// NR / N4: narrow records (8 B / 4 B for COUNT), V32: compact records carrying a value.
+// Written without branches: the callers classify 8 records back to back.
+template <bool NR, bool N4, bool V32>
+GW_HD int p1_lean(const P1Hot& h, int64_t key, int64_t ts, int64_t v) {
+    const uint64_t d = (uint64_t)ts - (uint64_t)h.t_late;
+    const bool below = ts < h.t_late, no_ts = ts == INT64_MIN;
+    const uint32_t q = udiv32((uint32_t)d, h.div);
+    const uint32_t rel = q - h.delta;  // q < delta wraps far above the ring (delta < 2^31)
+    bool fits;
+    if (NR) {
+        fits = (uint64_t)key < (uint64_t)(N4 ? kNarCountKeyLimit : kNarKeyLimit);
+        if (!N4) fits = fits && v >= -kNarValLimit && v < kNarValLimit;
+    } else {
+        fits = key != kEmptyKey;  // the sentinel key's slot is not in any region
+        if (V32) fits = fits && v >= INT32_MIN && v <= INT32_MAX;
+    }
+    const bool in_ring = !below && !no_ts && (uint32_t)(d >> 32) == 0 && q >= h.q_refire && rel < h.ring && fits;
+    uint32_t p = h.b_pos + rel;
+    if (p >= h.ring) p -= h.ring;
+    return in_ring ? (int)p : (below && !no_ts && h.late_plain) ? P1_LATE : P1_SPECIAL;
+}
+
 }  // namespace gw

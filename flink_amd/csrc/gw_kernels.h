@@ -152,6 +152,7 @@ struct IngestArgs {
     int64_t* rf_a1;
     int64_t* rf_seq;
     UDiv64 div;         // division by the pane width g
+    UDiv32 div32;       //   and of dividends below 2^32 (the lean pass 1, gw_pane.hip)
     int32_t b_pos;      // B mod R
     int32_t late_exact; // 0: t_late was clamped at Long.MIN_VALUE (then ts < t_late is a range error)
     PaneTable t;
@@ -164,7 +165,7 @@ struct IngestArgs {
     int32_t cls_j;
     // size < slide (gw_runtime.cpp: pane width = slide, one pane per window): a record whose
     // offset in its pane is >= gap_size lies between two windows and belongs to none
-    int64_t gap_w;      // pane width (= slide) when gap_size > 0
+    int64_t gap_w;      // pane width g, always set (= slide when gap_size > 0)
     int64_t gap_size;   // window size, 0: no gaps
     int64_t gap_late;   // a record in a gap is late iff ts <= gap_late (= watermark - lateness:
                         // isElementLate, WindowOperator.java:620-623)
@@ -355,7 +356,9 @@ hipError_t launch_ingest(const IngestArgs& a, int path, int unroll, hipStream_t 
 // e0 / e1 (timing, may be null): events stamped with the first kernel's start and the last
 // kernel's end of the launch (hipExtLaunchKernelGGL), so a timed launch measures its kernels
 // without the marker packets of hipEventRecord around them.
-hipError_t launch_region_p1(const IngestArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// *lean (may be null): 1 if the launch took k_rgn_p1_lean, 0 for the general k_rgn_p1
+hipError_t launch_region_p1(const IngestArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
+                            int* lean = nullptr);
 hipError_t launch_publish_status(const IngestArgs& a, hipStream_t s);
 // ... and, per flush, plan + P2 (two-pass tables) + apply over a.ntiles buffer tiles
 hipError_t launch_region_flush(const IngestArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

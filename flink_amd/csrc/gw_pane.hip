@@ -512,8 +512,7 @@ constexpr uint64_t kCmpSpill = 1ull << 63;
 // P2 and the apply recompute the key's hash (region bits, home slot) from it.  A record that
 // does not fit goes to the deferred list (exact); past 1/64 of a window's records the
 // handle drops to compact records at its next window.
-constexpr int kFmtWide = 0, kFmtCmp = 1, kFmtNar = 2;
-constexpr int64_t kNarKeyLimit = (1ll << 32) - 2, kNarCountKeyLimit = 1ll << 28, kNarValLimit = 1ll << 27;
+constexpr int kFmtWide = 0, kFmtCmp = 1, kFmtNar = 2;  // (the narrow limits: gw_common.h)
 __device__ __forceinline__ uint64_t nar_pack(int64_t key, int64_t v, uint32_t pos) {
     return (uint64_t)(uint32_t)key | ((uint64_t)(((uint32_t)(int32_t)v << 4) | pos) << 32);
 }
@@ -673,6 +672,130 @@ __device__ __forceinline__ void load_record(const IngestArgs& a, int64_t i, int6
     }
 }
 
+// Rare records of a P1 tile (deferred, re-fire, side output, the sentinel key) in a second
+// pass that only waves holding one run: it re-reads and classifies its items with the full
+// classify and writes them out, so the unrolled pass stays small.
+// LEAN = false: every item is classified again (classify is deterministic; the unrolled pass
+// took the late / flag / wide / occupancy counts).  LEAN = true: only the items the lean pass
+// marked special (bit `it` of spec), whose counts it did not take: they are taken here.
+template <int AGG, int FMT, bool GAP, bool LEAN, int THR, int IT>
+__device__ __forceinline__ void p1_rare(const IngestArgs& a_in, int64_t lo, int64_t hi, uint32_t spec,
+                                        unsigned long long& late, unsigned long long& flags,
+                                        unsigned long long& wide, unsigned long long& occ) {
+    constexpr bool C = FMT == kFmtCmp && cmp_agg<AGG>();
+    constexpr bool NR = FMT == kFmtNar && cmp_agg<AGG>();
+    constexpr bool N4 = NR && AGG == GW_COUNT;
+    constexpr bool ACC = !(C && AGG == GW_COUNT);
+    if (!__any(spec != 0)) return;
+    const IngestArgs& a = a_in;
+#pragma unroll 1
+    for (int it = 0; it < IT; ++it) {
+        const int64_t i = lo + it * THR + threadIdx.x;
+        int64_t k = 0, v0 = 0, v1 = 0, pane = 0;
+        uint32_t ps = 0;
+        int st = REC_SKIP;
+        if (i < hi && ((spec >> it) & 1u)) {
+            unsigned long long dl = 0, df = 0;
+            int64_t t, v;
+            load_record(a, i, k, t, v);
+            st = classify<AGG, GAP>(a, t, v, ps, pane, v0, v1, dl, df);
+            bool beyond = false;  // the compact record's 32-bit value, the narrow record's key / value
+            if (C && ACC && st == REC_RING && (v0 < INT32_MIN || v0 > INT32_MAX)) beyond = true;
+            if (NR && st == REC_RING &&
+                ((uint64_t)k >= (uint64_t)(N4 ? kNarCountKeyLimit : kNarKeyLimit) ||
+                 (!N4 && (v0 < -kNarValLimit || v0 >= kNarValLimit))))
+                beyond = true;
+            if (beyond) st = REC_DEFER;  // exact via the deferred list
+            // Not reached: p1hot_fits admits a launch only if every record the lean pass marks
+            // special and classify puts in the ring is one of the two cases above.  Kept as an
+            // exact fallback (the deferred list), since such a record has no rank in the tile.
+            if (LEAN && st == REC_RING && k != kEmptyKey) st = REC_DEFER;
+            if (st == REC_RING && k == kEmptyKey) {  // sentinel slot: straight atomics
+                cell_atomic<AGG>(pt_cell(a.t, a.t.cap, ps), v0, v1);
+                mask_set<AGG>(a.t, a.t.cap, ps);
+            }
+            if constexpr (LEAN) {
+                late += dl;
+                flags |= df;
+                if (beyond) wide++;
+                if (st == REC_RING) occ |= 1ull << ps;
+            }
+        }
+        defer_write(a, st == REC_DEFER, k, pane, v0, v1);
+        refire_write(a, st == REC_REFIRE, k, pane, v0, v1, i);
+        if (a.lo_key) late_write(a, st == REC_LATE, k, i);
+    }
+}
+
+// The rest of a P1 tile once every record has its bucket and rank (br: bucket << 16 | rank,
+// ~0: none): scan the bucket counts, sort the tile in LDS (s) and write it back (kout: the
+// tile's records in p1_key) with its descriptor row.
+template <int AGG, int FMT, int THR, int IT, typename V0>
+__device__ __forceinline__ void p1_finish(const IngestArgs& a, int64_t g, int64_t* kout, const int64_t (&key)[IT],
+                                          const V0 (&c0)[IT],
+                                          const int64_t (&c1)[IT], const uint32_t (&pos)[IT],
+                                          const uint32_t (&br)[IT], const TileLds& s, uint32_t* lh, uint32_t* ls,
+                                          unsigned long long* s_occ, unsigned long long occ,
+                                          unsigned long long wide, unsigned long long& occ_all) {
+    constexpr bool C = FMT == kFmtCmp && cmp_agg<AGG>();
+    constexpr bool NR = FMT == kFmtNar && cmp_agg<AGG>();
+    constexpr bool N4 = NR && AGG == GW_COUNT;  // 4-byte narrow records
+    constexpr bool AV = !C && !NR && (AGG == GW_AVG_I64 || AGG == GW_AVG_F64);
+    constexpr bool ACC = !(C && AGG == GW_COUNT);  // COUNT records carry no value
+    int32_t* s_v32 = reinterpret_cast<int32_t*>(s.a0);  // C: 32-bit values
+    uint32_t* s_r32 = reinterpret_cast<uint32_t*>(s.k);  // N4: the records
+    const int nb = 1 << a.d1_bits;
+    occ_all |= occ;
+    occ = wave_ior(occ);
+    if (__lane_id() == 0 && occ) atomicOr(s_occ, occ);
+    __syncthreads();
+    scan_buckets(lh, ls, nb);
+    if (threadIdx.x == 0 && *s_occ) atomicOr(a.batch_occ, *s_occ);
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        if (br[it] == ~0u) continue;
+        const uint32_t j = ls[br[it] >> 16] + (br[it] & 0xffffu);
+        if constexpr (N4) {
+            s_r32[j] = (uint32_t)key[it];
+            continue;
+        }
+        s.k[j] = key[it];
+        if constexpr (NR) continue;
+        if constexpr (C) {
+            if constexpr (ACC) s_v32[j] = c0[it];
+        } else {
+            s.a0[j] = c0[it];
+            if constexpr (AV) s.a1[j] = c1[it];
+            s.pos[j] = (uint8_t)pos[it];
+        }
+    }
+    __syncthreads();
+    const uint32_t cnt = ls[nb - 1] + lh[nb - 1];
+    const int64_t tile = a.tile0 + g;
+    const int64_t base = tile * kPartTile;
+    for (uint32_t j = threadIdx.x; j < cnt; j += THR) {
+        if constexpr (N4) {
+            __builtin_nontemporal_store(s_r32[j], reinterpret_cast<uint32_t*>(kout) + j);
+            continue;
+        }
+        __builtin_nontemporal_store((int64_t)s.k[j], kout + j);  // read back a flush later
+        if constexpr (NR) continue;
+        if constexpr (C) {
+            if constexpr (ACC) __builtin_nontemporal_store(s_v32[j], reinterpret_cast<int32_t*>(a.p1_a0) + base + j);
+        } else {
+            a.p1_a0[base + j] = s.a0[j];
+            if constexpr (AV) a.p1_a1[base + j] = s.a1[j];
+            a.p1_pos[base + j] = s.pos[j];
+        }
+    }
+    for (int b = threadIdx.x; b < nb; b += THR) a.p1_row[tile * kPartBuckets + b] = desc_pack(ls[b], lh[b]);
+    if constexpr ((C && ACC) || NR) {
+        wide = wave_sum(wide);
+        if (__lane_id() == 0 && wide) atomicAdd(&a.st->wide_vals, wide);
+    }
+}
+
 // P1 body for one tile: the records' inputs are in registers (item it of thread x is record
 // lo + it * THR + x); lh[] zeroed and s_occ cleared by the caller, with a barrier after.
 // Classifies, ranks by pass-1 bucket (LDS atomics), sorts the tile in LDS (s) and writes it
@@ -686,11 +809,7 @@ __device__ __forceinline__ void p1_tile(const IngestArgs& a, int64_t g, int64_t 
     constexpr bool C = FMT == kFmtCmp && cmp_agg<AGG>();
     constexpr bool NR = FMT == kFmtNar && cmp_agg<AGG>();
     constexpr bool N4 = NR && AGG == GW_COUNT;  // 4-byte narrow records
-    constexpr bool AV = !C && !NR && (AGG == GW_AVG_I64 || AGG == GW_AVG_F64);
     constexpr bool ACC = !(C && AGG == GW_COUNT);  // COUNT records carry no value
-    int32_t* s_v32 = reinterpret_cast<int32_t*>(s.a0);  // C: 32-bit values
-    uint32_t* s_r32 = reinterpret_cast<uint32_t*>(s.k);  // N4: the records
-    const int nb = 1 << a.d1_bits;
     unsigned long long occ = 0, wide = 0;
     bool special = false;
     // Registers per record after classification: the key (compact: the hash word), the
@@ -736,86 +855,10 @@ __device__ __forceinline__ void p1_tile(const IngestArgs& a, int64_t g, int64_t 
         pos[it] = ps;
         br[it] = bk >= 0 ? ((uint32_t)bk << 16) | atomicAdd(&lh[bk], 1u) : ~0u;
     }
-    // Rare records (deferred, re-fire, side output, the sentinel key) in a second pass that
-    // only waves holding one run: it re-reads and re-classifies its items (classify is
-    // deterministic; its late / flag counts were taken above) and writes them out, so the
-    // unrolled pass above stays small.
-    if (__any(special)) {
-#pragma unroll 1
-        for (int it = 0; it < IT; ++it) {
-            const int64_t i = lo + it * THR + threadIdx.x;
-            int64_t k = 0, v0 = 0, v1 = 0, pane = 0;
-            uint32_t ps = 0;
-            int st = REC_SKIP;
-            if (i < hi) {
-                unsigned long long dl = 0, df = 0;
-                int64_t t, v;
-                load_record(a, i, k, t, v);
-                st = classify<AGG, GAP>(a, t, v, ps, pane, v0, v1, dl, df);
-                if (C && ACC && st == REC_RING && (v0 < INT32_MIN || v0 > INT32_MAX)) st = REC_DEFER;
-                if (NR && st == REC_RING &&
-                    ((uint64_t)k >= (uint64_t)(N4 ? kNarCountKeyLimit : kNarKeyLimit) ||
-                     (!N4 && (v0 < -kNarValLimit || v0 >= kNarValLimit))))
-                    st = REC_DEFER;
-                if (st == REC_RING && k == kEmptyKey) {  // sentinel slot: straight atomics
-                    cell_atomic<AGG>(pt_cell(a.t, a.t.cap, ps), v0, v1);
-                    mask_set<AGG>(a.t, a.t.cap, ps);
-                }
-            }
-            defer_write(a, st == REC_DEFER, k, pane, v0, v1);
-            refire_write(a, st == REC_REFIRE, k, pane, v0, v1, i);
-            if (a.lo_key) late_write(a, st == REC_LATE, k, i);
-        }
-    }
-    occ_all |= occ;
-    occ = wave_ior(occ);
-    if (__lane_id() == 0 && occ) atomicOr(s_occ, occ);
-    __syncthreads();
-    scan_buckets(lh, ls, nb);
-    if (threadIdx.x == 0 && *s_occ) atomicOr(a.batch_occ, *s_occ);
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        if (br[it] == ~0u) continue;
-        const uint32_t j = ls[br[it] >> 16] + (br[it] & 0xffffu);
-        if constexpr (N4) {
-            s_r32[j] = (uint32_t)key[it];
-            continue;
-        }
-        s.k[j] = key[it];
-        if constexpr (NR) continue;
-        if constexpr (C) {
-            if constexpr (ACC) s_v32[j] = c0[it];
-        } else {
-            s.a0[j] = c0[it];
-            if constexpr (AV) s.a1[j] = c1[it];
-            s.pos[j] = (uint8_t)pos[it];
-        }
-    }
-    __syncthreads();
-    const uint32_t cnt = ls[nb - 1] + lh[nb - 1];
-    const int64_t tile = a.tile0 + g;
-    const int64_t base = tile * kPartTile;
-    for (uint32_t j = threadIdx.x; j < cnt; j += THR) {
-        if constexpr (N4) {
-            __builtin_nontemporal_store(s_r32[j], reinterpret_cast<uint32_t*>(a.p1_key) + base + j);
-            continue;
-        }
-        __builtin_nontemporal_store((int64_t)s.k[j], a.p1_key + base + j);  // read back a flush later
-        if constexpr (NR) continue;
-        if constexpr (C) {
-            if constexpr (ACC) __builtin_nontemporal_store(s_v32[j], reinterpret_cast<int32_t*>(a.p1_a0) + base + j);
-        } else {
-            a.p1_a0[base + j] = s.a0[j];
-            if constexpr (AV) a.p1_a1[base + j] = s.a1[j];
-            a.p1_pos[base + j] = s.pos[j];
-        }
-    }
-    for (int b = threadIdx.x; b < nb; b += THR) a.p1_row[tile * kPartBuckets + b] = desc_pack(ls[b], lh[b]);
-    if constexpr ((C && ACC) || NR) {
-        wide = wave_sum(wide);
-        if (__lane_id() == 0 && wide) atomicAdd(&a.st->wide_vals, wide);
-    }
+    p1_rare<AGG, FMT, GAP, false, THR, IT>(a, lo, hi, special ? ~0u : 0u, late, flags, wide, occ);
+    int64_t* kout = N4 ? reinterpret_cast<int64_t*>(reinterpret_cast<uint32_t*>(a.p1_key) + (a.tile0 + g) * kPartTile)
+                       : a.p1_key + (a.tile0 + g) * kPartTile;
+    p1_finish<AGG, FMT, THR, IT>(a, g, kout, key, c0, c1, pos, br, s, lh, ls, s_occ, occ, wide, occ_all);
 }
 
 template <int AGG, int FMT, bool GAP>
@@ -854,6 +897,138 @@ __global__ void __launch_bounds__(kPartThreads) GW_P1_ATTR k_rgn_p1(IngestArgs a
         }
     }
     p1_tile<AGG, FMT, GAP, kPartThreads, kPartItems>(a, g, lo, hi, key, ts, val, s, lh, ls, &s_occ, late, flags, occ);
+    block_commit(a.st, late, 0, flags, occ);
+}
+
+// The lean P1 (launch_region_p1 takes it whenever p1hot_fits: no gaps, no packed words, the
+// ring geometry in 32 bits).  Its unrolled pass reads only the P1Hot block h and decides only
+// the common outcomes (gw_common.h p1_lean: in ring, or late and merely counted) without a
+// branch; every other record is marked special and left, with its counts, to p1_rare's full
+// classify.  The ranking is a phase of its own: the 8 LDS atomics of a thread are issued back
+// to back and waited for once.  A record without a bucket adds into a dummy counter behind
+// lh[kPartBuckets] (one per lane, so a tile of such records does not serialise on one
+// address), so no branch surrounds the atomic; which of the three rows of dummy counters it
+// is says what the record was (beyond the batch, special, late), so the pass keeps one word
+// per record and takes the special bits and the late count from it after the atomics.  The
+// order of records inside a bucket of a tile is decided by a race between waves either way;
+// no result depends on it.
+constexpr int kP1Dummy = 3 * 64;
+template <int AGG, int FMT, int THR, int IT>
+__device__ __forceinline__ void p1_tile_lean(const P1Hot& h, const IngestArgs& a, int64_t g, uint32_t nrec,
+                                             int64_t (&key)[IT], const int64_t (&ts)[IT], const int64_t (&val)[IT],
+                                             const TileLds& s, uint32_t* lh, uint32_t* ls,
+                                             unsigned long long* s_occ, unsigned long long& late,
+                                             unsigned long long& flags, unsigned long long& occ_all,
+                                             const IngestArgs* cold) {
+    constexpr bool C = FMT == kFmtCmp && cmp_agg<AGG>();
+    constexpr bool NR = FMT == kFmtNar && cmp_agg<AGG>();
+    constexpr bool N4 = NR && AGG == GW_COUNT;
+    constexpr bool ACC = !(C && AGG == GW_COUNT);
+    unsigned long long occ = 0, wide = 0;
+    uint32_t spec = 0, nlate = 0;
+    using V0 = std::conditional_t<C, int32_t, int64_t>;
+    V0 c0[IT];
+    int64_t c1[IT];
+    uint32_t pos[IT], br[IT];
+    const uint32_t none = kPartBuckets + (threadIdx.x & 63u);
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const bool in = (uint32_t)(it * THR) + threadIdx.x < nrec;
+        const int st = p1_lean<NR, N4, C && ACC>(h, key[it], ts[it], val[it]);
+        const bool ring = in && st >= 0;
+        const uint32_t ps = ring ? (uint32_t)st : 0u;
+        occ |= ring ? 1ull << ps : 0ull;
+        int64_t v0, v1;
+        record_cell(AGG, val[it], v0, v1);
+        // (a narrow record's key is below 2^32: the hash's high-word products drop out)
+        const uint64_t hs = slot_hash(NR ? (int64_t)(uint64_t)(uint32_t)key[it] : key[it]);
+        const uint32_t hh = (uint32_t)(hs >> 32);
+        // pt_bucket, or the dummy counter of the record's kind (-P1_SPECIAL = 1, -P1_LATE = 2)
+        br[it] = ring ? (hh >> 1) >> h.bk_sh : none + (in ? (uint32_t)-st * 64u : 0u);
+        if constexpr (C)  // cmp_pack: the bucket bits of the high word give way to the position
+            key[it] = (int64_t)((uint64_t)(uint32_t)hs | (uint64_t)((hh & h.hmask) | ((ps << 1) << h.bk_sh)) << 32);
+        if constexpr (NR) key[it] = N4 ? (int64_t)nar_pack32(key[it], ps) : (int64_t)nar_pack(key[it], v0, ps);
+        c0[it] = (V0)v0;
+        c1[it] = v1;
+        pos[it] = ps;
+    }
+    uint32_t rk[IT];
+    __builtin_amdgcn_sched_barrier(0);  // nothing of what follows (LDS shuffles and their waits) among the atomics
+#pragma unroll
+    for (int it = 0; it < IT; ++it) rk[it] = atomicAdd(&lh[br[it]], 1u);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        spec |= br[it] - (kPartBuckets + 64u) < 64u ? 1u << it : 0u;
+        nlate += br[it] >= kPartBuckets + 128u;
+        br[it] = br[it] < (uint32_t)kPartBuckets ? (br[it] << 16) | rk[it] : ~0u;
+    }
+    late += nlate;
+    int64_t* kout = reinterpret_cast<int64_t*>(static_cast<char*>(h.out) + g * (kPartTile * (N4 ? 4 : 8)));
+    p1_finish<AGG, FMT, THR, IT>(a, g, kout, key, c0, c1, pos, br, s, lh, ls, s_occ, occ, 0, occ_all);
+    // The rare pass last, when the tile's registers are dead (its 64-bit divisions would set
+    // the kernel's register count otherwise); it needs nothing of the sort and the sort
+    // nothing of it.  Its ring positions (records of the sentinel key) and wide count go
+    // straight to the batch's words.
+    // It reads the arguments through a pointer the compiler cannot see through (the kernel's
+    // own argument block, k_rgn_p1_lean), so that they are loaded where the pass uses them:
+    // known to be kernel arguments, its ~50 fields are all loaded into scalar registers ahead
+    // of its loop, more than the scalar file holds, and the kernel spills.
+    occ = 0;
+    p1_rare<AGG, FMT, false, true, THR, IT>(*cold, g * kPartTile, g * kPartTile + nrec, spec, late, flags, wide, occ);
+    if (__any(spec != 0)) {
+        occ_all |= occ;
+        occ = wave_ior(occ);
+        wide = wave_sum(wide);
+        if (__lane_id() == 0 && occ) atomicOr(a.batch_occ, occ);
+        if (__lane_id() == 0 && wide) atomicAdd(&a.st->wide_vals, wide);
+    }
+}
+
+// The argument block of k_rgn_p1_lean as a struct (both members are trivially copyable
+// aggregates of 8-byte alignment: the block lays them out as a struct would).
+struct P1LeanArgs {
+    P1Hot h;
+    IngestArgs a;
+};
+static_assert(alignof(IngestArgs) == 8 && alignof(P1Hot) == 8 && sizeof(P1Hot) % 8 == 0 &&
+                  offsetof(P1LeanArgs, h) == 0 && offsetof(P1LeanArgs, a) == sizeof(P1Hot),
+              "kernel argument layout of k_rgn_p1_lean");
+template <int AGG, int FMT>
+__global__ void __launch_bounds__(kPartThreads) GW_P1_ATTR k_rgn_p1_lean(P1Hot h, IngestArgs a) {
+    constexpr bool C = FMT == kFmtCmp && cmp_agg<AGG>();
+    constexpr bool NR = FMT == kFmtNar && cmp_agg<AGG>();
+    constexpr bool AV = !C && !NR && (AGG == GW_AVG_I64 || AGG == GW_AVG_F64);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const TileLds s = tile_lds<AV>(smem);
+    __shared__ uint32_t lh[kPartBuckets + kP1Dummy], ls[kPartBuckets];
+    __shared__ unsigned long long s_occ;
+    const int64_t g = blockIdx.x;
+    const int64_t lo = g * kPartTile;
+    const uint32_t nrec = (uint32_t)min(h.n - lo, (int64_t)kPartTile);
+    if (g == 0 && threadIdx.x < 64 && a.st_host) publish_status_wave(a.st, a.st_host, a.st_seq);
+    for (int b = threadIdx.x; b < kPartBuckets + kP1Dummy; b += blockDim.x) lh[b] = 0;
+    if (threadIdx.x == 0) s_occ = 0;
+    __syncthreads();
+    unsigned long long late = 0, flags = 0, occ = 0;
+    int64_t key[kPartItems], ts[kPartItems], val[kPartItems];
+#pragma unroll
+    for (int it = 0; it < kPartItems; ++it) {  // all loads in flight first
+        const uint32_t x = (uint32_t)(it * kPartThreads) + threadIdx.x;
+        key[it] = 0; ts[it] = 0; val[it] = 0;
+        if (x < nrec) {
+            key[it] = __builtin_nontemporal_load(h.key + lo + x);  // read once: keep it out of the caches
+            ts[it] = __builtin_nontemporal_load(h.ts + lo + x);
+            if (h.val) val[it] = __builtin_nontemporal_load(h.val + lo + x);
+        }
+    }
+    // the IngestArgs of this launch as plain memory for the rare pass: the kernel's argument
+    // block holds the arguments in order, each at its natural alignment, as P1LeanArgs does
+    const IngestArgs* cold = reinterpret_cast<const IngestArgs*>(
+        (const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(P1LeanArgs, a));
+    asm volatile("" : "+s"(cold));
+    p1_tile_lean<AGG, FMT, kPartThreads, kPartItems>(h, a, g, nrec, key, ts, val, s, lh, ls, &s_occ, late, flags, occ,
+                                                     cold);
     block_commit(a.st, late, 0, flags, occ);
 }
 
@@ -3023,11 +3198,58 @@ int region_group(int d1_bits) {
     return std::max(1, std::min(kMaxGroup, 7 * (1 << d1_bits) * 4096 / (4 * kPartTile)));
 }
 
+// The lean P1's scalars from the launch's arguments; false where they do not fit it (gapped
+// panes, wide records, packed exchange words, a ring base or re-fire bound beyond 32 bits, a ring that ends
+// more than 2^32 ms after t_late), and the launch takes the general body.  With the last
+// condition a record whose ts - t_late needs more than 32 bits lies beyond the ring: it is
+// special because it is deferred, never because the lean pass cannot place it.
+// GW_P1_LEAN=0 (experiments) always takes the general body.
+static bool p1hot_fits(const IngestArgs& a, P1Hot& h) {
+    static const bool off = [] { const char* e = getenv("GW_P1_LEAN"); return e && atoi(e) == 0; }();
+    if (off || a.fmt == kFmtWide || a.gap_size || a.pk_w || a.delta >> 31 || a.q_refire >> 32 || a.t.ring < 1 || a.t.ring > kMaxRing ||
+        a.d1_bits != a.t.rb1 || a.t.rb1 < 0 || a.t.rb1 > 8 || a.gap_w < 1 ||
+        (unsigned __int128)(a.delta + (uint64_t)a.t.ring) * (uint64_t)a.gap_w > ((unsigned __int128)1 << 32))
+        return false;
+    const bool n4 = a.fmt == kFmtNar && a.t.agg == GW_COUNT;
+    h.key = a.key; h.ts = a.ts; h.val = a.val;
+    h.out = n4 ? (void*)(reinterpret_cast<uint32_t*>(a.p1_key) + a.tile0 * kPartTile)
+               : (void*)(a.p1_key + a.tile0 * kPartTile);
+    h.n = a.n;
+    h.t_late = a.t_late;
+    h.div = a.div32;
+    h.delta = (uint32_t)a.delta;
+    h.q_refire = (uint32_t)a.q_refire;
+    h.ring = (uint32_t)a.t.ring;
+    h.b_pos = (uint32_t)a.b_pos;
+    h.bk_sh = 31u - (uint32_t)a.t.rb1;
+    h.hmask = 0xffffffffu >> a.d1_bits;
+    h.late_plain = a.late_exact && !a.lo_key && a.cls_J <= 1;
+    return true;
+}
+
 // Region path, P1 over one watermark batch: one block per 4096-record tile.
-hipError_t launch_region_p1(const IngestArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+hipError_t launch_region_p1(const IngestArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1, int* lean) {
     const int64_t tiles = (a.n + kPartTile - 1) / kPartTile;
+    if (lean) *lean = 0;
     if (tiles == 0) return record_empty(s, e0, e1);
     const size_t part_lds = part_lds_bytes(a);
+    P1Hot hot{};
+    if (p1hot_fits(a, hot)) {
+        if (lean) *lean = 1;
+#define P1N(A, F)                                                                                             \
+    lds_opt_in((const void*)k_rgn_p1_lean<A, F>, part_lds);                                                    \
+    GW_TLAUNCH((k_rgn_p1_lean<A, F>), dim3((unsigned)tiles), dim3(kPartThreads), part_lds, s, e0, e1, hot, a)
+#define L(A)                                  \
+    if (a.fmt == kFmtNar) {                   \
+        P1N(A, kFmtNar);                      \
+    } else {                                  \
+        P1N(A, kFmtCmp);                      \
+    }
+        GW_AGG_SWITCH(a.t.agg, L);
+#undef L
+#undef P1N
+        return hipGetLastError();
+    }
     // beyond the 64 KB default: opt in (gfx950 has 160 KB of LDS per CU)
     // the gap test (size < slide) only in a variant of its own: it costs the hot pass ~3%
 #define P1L(A, F, G)                                                                                            \

@@ -85,7 +85,10 @@ int64_t gcd64(int64_t a, int64_t b) {
 }
 bool fits64(i128 v) { return v >= (i128)INT64_MIN && v <= (i128)INT64_MAX; }
 
-UDiv64 make_udiv(uint64_t d) {
+// Both forms of the division by d: 64-bit dividends, and (gw_common.h make_udiv32) dividends
+// known to be below 2^32.
+UDiv64 make_udiv(uint64_t d, UDiv32& d32) {
+    d32 = make_udiv32(d);
     UDiv64 r{};
     if (d == 1) { r.mode = 1; return r; }
     unsigned l = 0;
@@ -255,6 +258,7 @@ struct gw_handle {
     int64_t gap_size = 0;  // size < slide: panes of width slide, records past `size` into one are skipped
     int R = 2;
     UDiv64 div{};
+    UDiv32 div32{};
 
     // state table (region-major SoA, gw_kernels.h)
     PaneTable tv{};
@@ -1214,6 +1218,7 @@ struct gw_handle {
         a.p_late = (int64_t)pl;
         a.delta = (uint64_t)(B - pl);
         a.div = div;
+        a.div32 = div32;
         a.b_pos = (int32_t)pos_of(B);
         a.late_exact = exact;
         a.t = tv;
@@ -1555,13 +1560,16 @@ struct gw_handle {
             stats.region_format = buf_fmt;
             if (buffered) arm_status(a);
             hp.lap(13);
+            int lean = 0;
             if (timing && (timing_ctr++ % timing_every) == 0) {  // every timing_every-th batch
                 auto ev = t_ingest.get();
-                HIPCHECK(launch_region_p1(a, stream, ev.first, ev.second));
+                HIPCHECK(launch_region_p1(a, stream, ev.first, ev.second, &lean));
                 t_ingest.pending.push_back(ev);
             } else {
-                HIPCHECK(launch_region_p1(a, stream));
+                HIPCHECK(launch_region_p1(a, stream, nullptr, nullptr, &lean));
             }
+            p1_lean += lean;
+            p1_general += !lean;
             nseg++;
             buf_tiles += tiles;
             buf_recs += nrec;
@@ -2466,6 +2474,8 @@ struct gw_handle {
     int64_t fast_fires = 0;  // fires enqueued behind their flush (gw_kernel_time_ms which = 3)
     int64_t fused_fires = 0;  // those of them whose rows the flush's apply emitted (which = 4)
     int64_t fused_revoked = 0;  // fused fires a guard or a full row buffer revoked (which = 5)
+    int64_t p1_lean = 0;        // region P1 launches that took k_rgn_p1_lean (which = 9)
+    int64_t p1_general = 0;     //   and those that took the general k_rgn_p1 (which = 10)
     // The common fire -- no lateness, no restored windows, nothing deferred, one pass of
     // windows starting at fired_k -- enqueued right behind the flush that precedes it, with
     // k_fire_guard between them: ONE host round trip per watermark instead of two (the flush's
@@ -2895,7 +2905,7 @@ int gw_create(const gw_config* cfg, gw_handle** out) {
     if (R > kMaxRing) R = kMaxRing;
     h->R = R;
     h->tv.ring = R;
-    h->div = make_udiv((uint64_t)h->g);
+    h->div = make_udiv((uint64_t)h->g, h->div32);
     h->fired_k = h->k_for_wm(INT64_MIN) + 1;
     h->B = h->fired_k * h->m;
     rc = h->alloc_table(h->tv, h->tv_mem, std::max<int64_t>(1024, (int64_t)((double)hint / gw_handle::kTableLoad) + 1));
@@ -5028,9 +5038,9 @@ int gw_kernel_time_ms(gw_handle* h, int which, double* ms, int64_t* launches) {
     }
     hipStreamSynchronize(h->stream);
     if (h->sess) return session_kernel_time(h->sess, which, ms, launches);
-    if (which >= 3 && which <= 5) {
+    if ((which >= 3 && which <= 5) || which == 9 || which == 10) {
         if (ms) *ms = 0.0;
-        if (launches) *launches = which == 3 ? h->fast_fires : which == 4 ? h->fused_fires : h->fused_revoked;
+        if (launches) *launches = which == 9 ? h->p1_lean : which == 10 ? h->p1_general : which == 3 ? h->fast_fires : which == 4 ? h->fused_fires : h->fused_revoked;
         return GW_OK;
     }
     KernelTimer& t = which == 0 ? h->t_ingest : which == 1 ? h->t_fire : h->t_apply;

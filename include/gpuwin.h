@@ -620,7 +620,9 @@ void* gw_stream(gw_handle* h);
  * which = 5: *launches = the fused fires that were revoked (their rows dropped, the windows
  * fired the exact way instead), *ms = 0.
  * which = 6, 7, 8 (session handles, timing enabled with 2): the ingest's slot lookup (prep),
- * grouping sort and per-key replay (segment), per launch; parts of which = 0. */
+ * grouping sort and per-key replay (segment), per launch; parts of which = 0.
+ * which = 9, 10 (pane handles): *launches = the region pass-1 launches so far that took the lean
+ * kernel (9) and the general one (10), *ms = 0; not reset by the call. */
 int  gw_kernel_time_ms(gw_handle* h, int which, double* ms, int64_t* launches);
 /* enable: 0 off, 1 every launch, k > 1: the region path's pass 1 (one launch per batch, all
  * alike) is timed on every k-th batch only (two event records per timed launch cost host

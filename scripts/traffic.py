@@ -26,6 +26,7 @@ for f in glob.glob(os.path.join(root, "pmc_*", "run_counter_collection.csv")):
         if c not in tot:
             continue
         name = r["Kernel_Name"].split("(")[0].replace("void gw::", "").replace("gw::", "").split("<")[0]
+        name = "k_rgn_p1" if name == "k_rgn_p1_lean" else name  # pass 1, whichever body the launch took
         if name not in PIPE:
             continue
         tot[c][name] = tot[c].get(name, 0.0) + float(r["Counter_Value"]) * 1024
