@@ -66,7 +66,13 @@ EXPORTS = [
     "gw_rows_serialized_device",
     "gw_valve_create", "gw_valve_destroy", "gw_valve_input", "gw_decode_channels_device",
     "gw_set_input_channels", "gw_ingest_channels", "gw_ingest_channels_device", "gw_input_status",
+    "gw_window_join_device", "gw_window_join_device_timed", "gw_window_join_host",
+    "gw_join_create", "gw_join_destroy", "gw_join_last_error", "gw_join_ingest", "gw_join_ingest_device",
+    "gw_join_advance_watermark", "gw_join_end_input", "gw_join_pending", "gw_join_drain", "gw_join_rows_device",
+    "gw_join_clear_rows", "gw_join_late_dropped", "gw_join_get_stats", "gw_join_stream",
 ]
+JOIN_MAX_WINDOWS = 64  # gpuwin.h GW_JOIN_MAX_WINDOWS
+JOIN_LEFT, JOIN_RIGHT = 0, 1
 EXCHANGE_ID_BYTES = 128
 EXCHANGE_RECV_SETS = 3  # gpuwin.h GW_EXCHANGE_RECV_SETS
 
@@ -166,6 +172,23 @@ class GwStats(ctypes.Structure):
         "events_in", "late_dropped", "rows_fired", "live_keys", "table_capacity", "table_bytes",
         "deferred", "batches", "fires", "rehashes", "preagg_batches", "session_merges", "applies",
         "region_format", "session_punted", "session_slow")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GwJoinConfig(ctypes.Structure):
+    _fields_ = [
+        ("assigner", ctypes.c_int32), ("size", ctypes.c_int64), ("slide", ctypes.c_int64),
+        ("offset", ctypes.c_int64), ("device", ctypes.c_int32), ("capacity_hint", ctypes.c_int64),
+        ("max_batch", ctypes.c_int64),
+    ]
+
+
+class GwJoinStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "live_left", "live_right", "log_capacity_left", "log_capacity_right", "fires", "pairs_fired",
+        "log_growths", "last_fire_tuples")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -296,6 +319,25 @@ def lib() -> ctypes.CDLL:
         "gw_ingest_channels": (c_int, [p, i32, p, p, p, ctypes.POINTER(GwRecordLayout), p, P64]),
         "gw_ingest_channels_device": (c_int, [p, i32, p, p, p, ctypes.POINTER(GwRecordLayout), p, p, P64]),
         "gw_input_status": (c_int, [p, P64, ctypes.POINTER(i32)]),
+        "gw_window_join_device": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, p, p, p, p, p, i64, P64, p]),
+        "gw_window_join_device_timed": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, p, p, p, p, p, i64,
+                                                P64, p, ctypes.POINTER(ctypes.c_double)]),
+        "gw_window_join_host": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, p, p, p, p, p, i64, P64]),
+        "gw_join_create": (c_int, [ctypes.POINTER(GwJoinConfig), ctypes.POINTER(p)]),
+        "gw_join_destroy": (c_int, [p]),
+        "gw_join_last_error": (ctypes.c_char_p, [p]),
+        "gw_join_ingest": (c_int, [p, i32, i64, p, p, p]),
+        "gw_join_ingest_device": (c_int, [p, i32, i64, p, p, p, p]),
+        "gw_join_advance_watermark": (c_int, [p, i64, P64]),
+        "gw_join_end_input": (c_int, [p, P64]),
+        "gw_join_pending": (c_int, [p, P64]),
+        "gw_join_drain": (c_int, [p, p, p, p, p, p, i64, P64]),
+        "gw_join_rows_device": (c_int, [p, ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p),
+                                        ctypes.POINTER(p), P64]),
+        "gw_join_clear_rows": (c_int, [p]),
+        "gw_join_late_dropped": (i64, [p]),
+        "gw_join_get_stats": (c_int, [p, ctypes.POINTER(GwJoinStats)]),
+        "gw_join_stream": (p, [p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -1,0 +1,1211 @@
+// gw_join.hip — event-time window join of two keyed streams (include/gpuwin.h gw_window_join_*,
+// gw_join_*): stream.join(other).where(k1).equalTo(k2).window(assigner).apply(JoinFunction),
+// Nexmark Q8.
+//
+// Flink runs a window join as union -> keyBy -> WindowOperator with ListState, and at the fire
+// JoinCoGroupFunction emits the per-(key, window) cross product of the two sides
+// (RS/api/datastream/JoinedStreams.java, CoGroupedStreams.java).  Here a fire over the records
+// of both sides and the watermark interval (w0, w1] is six stages over device columns:
+//
+//   count    per record the number of its windows with w0 < end - 1 <= w1, an exclusive scan of
+//            those counts, and the device-wide minimum / maximum of the fired window starts and
+//            of the fired records' key words (so the sort sees only the bits that vary);
+//   emit     one tuple per (record, fired window): the key word (sign bit flipped, minus the
+//            minimum), the window ordinal (start - min start) / slide and a source word (side in
+//            the top bit, record index below); left tuples before right tuples, arrival order;
+//   sort     two stable passes of gw::sort_pairs_u64 -- by key word, then by ordinal -- so a
+//            (window, key) group is contiguous, windows ascending, keys ascending, and inside a
+//            group the left records precede the right ones, each side in arrival order;
+//   groups   heads where (ordinal, key) changes; per group its first tuple, L and R; an int64
+//            exclusive scan of L * R.  This table is a stage of its own (a coGroup or an outer
+//            join reads the same table).  Groups with L * R > 0 are compacted into descriptors;
+//   expand   the hot kernel: a workgroup owns kExpTile consecutive output pairs, finds the
+//            descriptors its tile touches with one search per end of the tile, keeps them in LDS,
+//            and every lane writes two consecutive pairs of each of the five columns with one
+//            16-byte store.  Work is split by output pairs, never by groups, so one group of
+//            4096 x 64 and a million groups of 1 x 1 are the same work per workgroup.
+//
+// No atomics in the expand kernel; the scans are two-pass (block sums, one block over the sums,
+// a down-sweep); the only look-back is gw_sort.hip's own.  The host reads the device twice per
+// call: the tuple count (it sizes the sort) and the pair count (it sizes the output).
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "gw_devmem.h"
+#include "gw_kernels.h"
+#include "gw_sort.h"
+
+namespace gw {
+
+struct JoinGeom {
+    int64_t size, slide, offset;
+};
+
+constexpr int kJoinThreads = 256;
+constexpr int kJoinMaxBlocks = 2048;  // grid-stride kernels that end in a few atomics per block
+constexpr uint32_t kJoinRight = 0x80000000u;
+// header words (int64) shared by the stages of one call
+enum { JH_NT = 0, JH_MINS, JH_MAXS, JH_MINK, JH_MAXK, JH_FLAGS, JH_NG, JH_TOTAL, JH_NC, JH_KEPT, JH_LATE, kJoinHdr = 16 };
+
+// SlidingEventTimeWindows.assignWindows (RS/api/windowing/assigners/SlidingEventTimeWindows.java:
+// 75-90) with TimeWindow.getWindowStartWithOffset (TimeWindow.java:264-272): the record's last
+// window start and the number of its windows (starts ls - k * slide, k < nw).  A step that leaves
+// int64 is GW_DF_RANGE instead of Java's wrap-around.
+GW_HD unsigned join_windows(const JoinGeom& g, int64_t ts, int64_t& ls, int& nw) {
+    ls = 0;
+    nw = 0;
+    if (ts == INT64_MIN) return (unsigned)GW_DF_NO_TS;
+    int64_t rel, end;
+    if (__builtin_sub_overflow(ts, g.offset, &rel)) return (unsigned)GW_DF_RANGE;
+    int64_t rem = rel % g.slide;
+    if (rem < 0) rem += g.slide;
+    if (__builtin_sub_overflow(ts, rem, &ls) || __builtin_add_overflow(ls, g.size, &end)) return (unsigned)GW_DF_RANGE;
+    if (g.size <= rem) return 0;  // size < slide: between two windows
+    nw = g.size == g.slide ? 1 : (int)(((uint64_t)(g.size - rem) + (uint64_t)(g.slide - 1)) / (uint64_t)g.slide);
+    int64_t back, first;
+    if (__builtin_mul_overflow((int64_t)(nw - 1), g.slide, &back) || __builtin_sub_overflow(ls, back, &first))
+        return (unsigned)GW_DF_RANGE;
+    return 0;
+}
+// Windows k of the record firing in (w0, w1] (EventTimeTrigger: at maxTimestamp = end - 1).
+GW_HD uint64_t join_fired(const JoinGeom& g, int64_t ls, int nw, int64_t w0, int64_t w1) {
+    uint64_t m = 0;
+    for (int k = 0; k < nw; ++k) {
+        const int64_t mt = ls - (int64_t)k * g.slide + (g.size - 1);
+        if (mt > w0 && mt <= w1) m |= 1ull << k;
+    }
+    return m;
+}
+GW_HD uint64_t join_key_word(int64_t key) { return (uint64_t)key ^ 0x8000000000000000ull; }
+
+// ---- scans --------------------------------------------------------------------------------
+constexpr int kScanTile = kJoinThreads * 4;
+
+__device__ __forceinline__ int64_t block_scan256(int64_t v, int64_t& total) {
+    __shared__ int64_t s_w[4];
+    const int lane = __lane_id(), wave = threadIdx.x >> 6;
+    int64_t incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int64_t up = (int64_t)__shfl_up((long long)incl, o);
+        if (lane >= o) incl += up;
+    }
+    __syncthreads();  // an earlier call's readers are done with s_w
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    int64_t base = 0;
+    total = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) base += s_w[w];
+        total += s_w[w];
+    }
+    return base + incl - v;
+}
+
+template <typename TIn>
+__global__ void __launch_bounds__(kJoinThreads) k_scan_reduce(const TIn* __restrict__ in, int64_t n, int64_t* blk) {
+    const int64_t i0 = (int64_t)blockIdx.x * kScanTile + threadIdx.x * 4;
+    int64_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j < n) v += (int64_t)in[i0 + j];
+    int64_t total;
+    block_scan256(v, total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(kJoinThreads) k_scan_blocks(int64_t* blk, int64_t nb, int64_t* total_out) {
+    const int64_t per = (nb + kJoinThreads - 1) / kJoinThreads;
+    const int64_t lo = std::min<int64_t>(nb, threadIdx.x * per), hi = std::min<int64_t>(nb, lo + per);
+    int64_t v = 0;
+    for (int64_t i = lo; i < hi; ++i) v += blk[i];
+    int64_t total;
+    int64_t run = block_scan256(v, total);
+    for (int64_t i = lo; i < hi; ++i) {
+        const int64_t x = blk[i];
+        blk[i] = run;
+        run += x;
+    }
+    if (threadIdx.x == 0) *total_out = total;
+}
+template <typename TIn, typename TOut>
+__global__ void __launch_bounds__(kJoinThreads) k_scan_down(const TIn* __restrict__ in, int64_t n,
+                                                             const int64_t* __restrict__ blk, TOut* out) {
+    const int64_t i0 = (int64_t)blockIdx.x * kScanTile + threadIdx.x * 4;
+    int64_t x[4], v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        x[j] = i0 + j < n ? (int64_t)in[i0 + j] : 0;
+        v += x[j];
+    }
+    int64_t total;
+    int64_t run = blk[blockIdx.x] + block_scan256(v, total);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (i0 + j < n) out[i0 + j] = (TOut)run;
+        run += x[j];
+    }
+}
+static int64_t scan_blocks(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+// out[i] = in[0] + ... + in[i - 1]; *total = the sum; blk: scan_blocks(n) words.
+template <typename TIn, typename TOut>
+static hipError_t scan_excl(const TIn* in, TOut* out, int64_t n, int64_t* blk, int64_t* total, hipStream_t s) {
+    const int64_t nb = scan_blocks(n);
+    if (nb > 0) hipLaunchKernelGGL(k_scan_reduce<TIn>, dim3((unsigned)nb), dim3(kJoinThreads), 0, s, in, n, blk);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kJoinThreads), 0, s, blk, nb, total);
+    if (nb > 0)
+        hipLaunchKernelGGL((k_scan_down<TIn, TOut>), dim3((unsigned)nb), dim3(kJoinThreads), 0, s, in, n, blk, out);
+    return hipGetLastError();
+}
+
+// ---- count / emit ---------------------------------------------------------------------------
+struct JoinIn {
+    const int64_t *key[2], *ts[2], *pay[2];
+    int64_t n_l, n;  // left records, all records (left first)
+    JoinGeom g;
+    int64_t w0, w1;
+};
+
+__device__ __forceinline__ int64_t wave_min_i64(int64_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const int64_t x = (int64_t)__shfl_xor((long long)v, o);
+        v = x < v ? x : v;
+    }
+    return v;
+}
+__device__ __forceinline__ int64_t wave_max_i64(int64_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const int64_t x = (int64_t)__shfl_xor((long long)v, o);
+        v = x > v ? x : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t x = (uint64_t)__shfl_xor((unsigned long long)v, o);
+        v = x < v ? x : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t x = (uint64_t)__shfl_xor((unsigned long long)v, o);
+        v = x > v ? x : v;
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(kJoinThreads) k_join_hdr_init(int64_t* hdr) {
+    if (threadIdx.x >= kJoinHdr) return;
+    int64_t v = 0;
+    if (threadIdx.x == JH_MINS) v = INT64_MAX;
+    if (threadIdx.x == JH_MAXS) v = INT64_MIN;
+    if (threadIdx.x == JH_MINK) v = -1;  // all ones
+    hdr[threadIdx.x] = v;
+}
+
+__global__ void __launch_bounds__(kJoinThreads) k_join_count(JoinIn a, uint32_t* cnt, int64_t* hdr) {
+    using ull = unsigned long long;
+    __shared__ int64_t s_min[4], s_max[4];
+    __shared__ uint64_t s_kmin[4], s_kmax[4], s_flags[4];
+    int64_t mins = INT64_MAX, maxs = INT64_MIN;
+    uint64_t mink = ~0ull, maxk = 0, flags = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kJoinThreads) {
+        const int side = i >= a.n_l;
+        const int64_t j = side ? i - a.n_l : i;
+        int64_t ls;
+        int nw;
+        const unsigned f = join_windows(a.g, a.ts[side][j], ls, nw);
+        flags |= f;
+        uint32_t c = 0;
+        if (!f) {
+            const uint64_t m = join_fired(a.g, ls, nw, a.w0, a.w1);
+            if (m) {
+                c = (uint32_t)__popcll(m);
+                const int klo = __ffsll((long long)m) - 1, khi = 63 - __clzll((long long)m);
+                const int64_t hi_s = ls - (int64_t)klo * a.g.slide, lo_s = ls - (int64_t)khi * a.g.slide;
+                mins = lo_s < mins ? lo_s : mins;
+                maxs = hi_s > maxs ? hi_s : maxs;
+                const uint64_t kw = join_key_word(a.key[side][j]);
+                mink = kw < mink ? kw : mink;
+                maxk = kw > maxk ? kw : maxk;
+            }
+        }
+        cnt[i] = c;
+    }
+    mins = wave_min_i64(mins);
+    maxs = wave_max_i64(maxs);
+    mink = wave_min_u64(mink);
+    maxk = wave_max_u64(maxk);
+    flags = wave_ior(flags);
+    const int wave = threadIdx.x >> 6;
+    if (__lane_id() == 0) {
+        s_min[wave] = mins; s_max[wave] = maxs; s_kmin[wave] = mink; s_kmax[wave] = maxk; s_flags[wave] = flags;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 4; ++w) {
+        mins = s_min[w] < mins ? s_min[w] : mins;
+        maxs = s_max[w] > maxs ? s_max[w] : maxs;
+        mink = s_kmin[w] < mink ? s_kmin[w] : mink;
+        maxk = s_kmax[w] > maxk ? s_kmax[w] : maxk;
+        flags |= s_flags[w];
+    }
+    if (flags) atomicOr((ull*)&hdr[JH_FLAGS], (ull)flags);
+    if (mins <= maxs) {  // the block saw a fired window
+        atomicMin((long long*)&hdr[JH_MINS], (long long)mins);
+        atomicMax((long long*)&hdr[JH_MAXS], (long long)maxs);
+        atomicMin((ull*)&hdr[JH_MINK], (ull)mink);
+        atomicMax((ull*)&hdr[JH_MAXK], (ull)maxk);
+    }
+}
+
+__global__ void __launch_bounds__(kJoinThreads) k_join_emit(JoinIn a, const uint32_t* __restrict__ toff, int64_t min_start,
+                                                            uint64_t min_kw, uint64_t* kw, uint64_t* ord, uint32_t* src) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kJoinThreads) {
+        const int side = i >= a.n_l;
+        const int64_t j = side ? i - a.n_l : i;
+        int64_t ls;
+        int nw;
+        if (join_windows(a.g, a.ts[side][j], ls, nw)) continue;
+        uint64_t m = join_fired(a.g, ls, nw, a.w0, a.w1);
+        if (!m) continue;
+        const uint64_t k = join_key_word(a.key[side][j]) - min_kw;
+        const uint32_t sw = (uint32_t)j | (side ? kJoinRight : 0u);
+        uint32_t t = toff[i];
+        while (m) {
+            const int q = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int64_t start = ls - (int64_t)q * a.g.slide;
+            kw[t] = k;
+            ord[t] = ((uint64_t)start - (uint64_t)min_start) / (uint64_t)a.g.slide;
+            src[t] = sw;
+            ++t;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kJoinThreads) k_join_gather_ord(int64_t nt, const uint32_t* __restrict__ perm,
+                                                                  const uint64_t* __restrict__ ord, uint64_t* out) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < nt; i += (int64_t)gridDim.x * kJoinThreads)
+        out[i] = ord[perm[i]];
+}
+
+// Sorted tuple i: its key, ordinal, source word and payload, and whether a group starts at it.
+__global__ void __launch_bounds__(kJoinThreads) k_join_gather(JoinIn a, int64_t nt, const uint32_t* __restrict__ perm,
+                                                              const uint64_t* __restrict__ ord,
+                                                              const uint32_t* __restrict__ src, int64_t* gkey, uint64_t* gord,
+                                                              uint32_t* gsrc, int64_t* gpay) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < nt; i += (int64_t)gridDim.x * kJoinThreads) {
+        const uint32_t t = perm[i];
+        const uint32_t sw = src[t];
+        const int side = sw >> 31;
+        const uint32_t j = sw & ~kJoinRight;
+        gkey[i] = a.key[side][j];
+        gord[i] = ord[t];
+        gsrc[i] = sw;
+        gpay[i] = a.pay[side][j];
+    }
+}
+
+// ---- group table ----------------------------------------------------------------------------
+__global__ void __launch_bounds__(kJoinThreads) k_join_heads(int64_t nt, const int64_t* __restrict__ gkey,
+                                                             const uint64_t* __restrict__ gord, uint32_t* head) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < nt; i += (int64_t)gridDim.x * kJoinThreads)
+        head[i] = i == 0 || gkey[i] != gkey[i - 1] || gord[i] != gord[i - 1];
+}
+// gfirst[g]: the group's first tuple; gmid[g]: its first right tuple (stays ~0 without one).
+__global__ void __launch_bounds__(kJoinThreads) k_join_group_fill(int64_t nt, const uint32_t* __restrict__ head,
+                                                                  const uint32_t* __restrict__ hex,
+                                                                  const uint32_t* __restrict__ gsrc, uint32_t* gfirst,
+                                                                  uint32_t* gmid) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < nt; i += (int64_t)gridDim.x * kJoinThreads) {
+        const uint32_t h = head[i];
+        const uint32_t g = hex[i] + h - 1;
+        if (h) gfirst[g] = (uint32_t)i;
+        if ((gsrc[i] >> 31) && (h || !(gsrc[i - 1] >> 31))) gmid[g] = (uint32_t)i;
+    }
+}
+// Over nt entries (the groups are the first hdr[JH_NG] of them): L * R and whether it is > 0.
+__global__ void __launch_bounds__(kJoinThreads) k_join_group_prod(int64_t nt, const int64_t* __restrict__ hdr,
+                                                                  const uint32_t* __restrict__ gfirst,
+                                                                  const uint32_t* __restrict__ gmid, int64_t* prod,
+                                                                  uint32_t* ne) {
+    const int64_t ng = hdr[JH_NG];
+    for (int64_t g = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; g < nt; g += (int64_t)gridDim.x * kJoinThreads) {
+        int64_t p = 0;
+        if (g < ng) {
+            const int64_t first = gfirst[g], end = g + 1 < ng ? (int64_t)gfirst[g + 1] : nt;
+            const int64_t mid = gmid[g] == ~0u ? end : (int64_t)gmid[g];
+            p = (mid - first) * (end - mid);  // both below 2^30
+        }
+        prod[g] = p;
+        ne[g] = p > 0;
+    }
+}
+// Descriptors of the groups with pairs: pair offset, first left tuple, first right tuple, R, key
+// and window start; coff[nc] = the total.
+__global__ void __launch_bounds__(kJoinThreads) k_join_compact(int64_t nt, const int64_t* __restrict__ hdr,
+                                                               const uint32_t* __restrict__ gfirst,
+                                                               const uint32_t* __restrict__ gmid,
+                                                               const int64_t* __restrict__ prod,
+                                                               const int64_t* __restrict__ poff,
+                                                               const uint32_t* __restrict__ cidx,
+                                                               const int64_t* __restrict__ gkey,
+                                                               const uint64_t* __restrict__ gord, int64_t min_start,
+                                                               int64_t slide, int64_t* coff, uint32_t* cfirst, uint32_t* crb,
+                                                               uint32_t* cR, int64_t* ckey, int64_t* cws) {
+    const int64_t ng = hdr[JH_NG];
+    for (int64_t g = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; g < ng; g += (int64_t)gridDim.x * kJoinThreads) {
+        if (g == 0) coff[hdr[JH_NC]] = hdr[JH_TOTAL];
+        if (prod[g] <= 0) continue;
+        const uint32_t c = cidx[g];
+        const int64_t first = gfirst[g], end = g + 1 < ng ? (int64_t)gfirst[g + 1] : nt;
+        coff[c] = poff[g];
+        cfirst[c] = (uint32_t)first;
+        crb[c] = gmid[g];
+        cR[c] = (uint32_t)(end - (int64_t)gmid[g]);
+        ckey[c] = gkey[first];
+        cws[c] = (int64_t)((uint64_t)min_start + gord[first] * (uint64_t)slide);
+    }
+}
+
+// ---- expand ---------------------------------------------------------------------------------
+constexpr int kExpTile = 1024;  // output slots per workgroup: 2 steps of 256 lanes x 2 pairs
+struct alignas(16) I64x2 {
+    int64_t a, b;
+};
+struct JoinOut {
+    int64_t* col[5];  // key, start, end, left payload, right payload
+};
+
+// One wave: the largest c in [0, nc) with coff[c] <= p (coff[0] = 0 <= p), 64 probes a round.
+__device__ __forceinline__ int64_t wave_search(const int64_t* __restrict__ coff, int64_t nc, int64_t p) {
+    const int lane = __lane_id();
+    int64_t lo = 0, hi = nc;
+    while (hi - lo > 1) {
+        const int64_t step = (hi - lo + 63) / 64;
+        const int64_t idx = lo + lane * step;
+        const bool ok = idx < hi && coff[idx] <= p;
+        const int k = (int)__popcll(__ballot(ok)) - 1;  // the probes that hold are a prefix of the lanes
+        lo += k * step;
+        hi = std::min<int64_t>(hi, lo + step);
+    }
+    return lo;
+}
+
+struct Pair {
+    int64_t key, ws, lp, rp;
+};
+
+// Output slot q holds pair q - shift: with shift = 1 the columns start 8 bytes past a 16-byte
+// boundary and pair 0 is written alone, so every two-pair store is aligned.
+template <bool VEC>
+__global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shift, int64_t nc,
+                                                              const int64_t* __restrict__ coff,
+                                                              const uint32_t* __restrict__ cfirst,
+                                                              const uint32_t* __restrict__ crb,
+                                                              const uint32_t* __restrict__ cR,
+                                                              const int64_t* __restrict__ ckey,
+                                                              const int64_t* __restrict__ cws,
+                                                              const int64_t* __restrict__ gpay, int64_t size, JoinOut o) {
+    __shared__ int64_t s_off[kExpTile + 1];
+    __shared__ uint32_t s_first[kExpTile], s_rb[kExpTile], s_R[kExpTile];
+    __shared__ int64_t s_c[2];
+    const int64_t slot0 = (int64_t)blockIdx.x * kExpTile;
+    const int64_t p_first = std::max<int64_t>(slot0 - shift, 0);
+    const int64_t p_last = std::min<int64_t>(slot0 + kExpTile - 1 - shift, P - 1);
+    const int wave = threadIdx.x >> 6;
+    if (wave < 2) {
+        const int64_t c = wave_search(coff, nc, wave == 0 ? p_first : p_last);
+        if (__lane_id() == 0) s_c[wave] = c;
+    }
+    __syncthreads();
+    const int64_t c0 = s_c[0];
+    const int ngt = (int)(s_c[1] - c0) + 1;  // <= kExpTile: every descriptor has a pair in the tile
+    for (int i = threadIdx.x; i <= ngt; i += kJoinThreads) {
+        s_off[i] = coff[c0 + i];
+        if (i < ngt) {
+            s_first[i] = cfirst[c0 + i];
+            s_rb[i] = crb[c0 + i];
+            s_R[i] = cR[c0 + i];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < kExpTile / (2 * kJoinThreads); ++step) {
+        const int64_t q = slot0 + step * 2 * kJoinThreads + 2 * threadIdx.x;
+        const int64_t pa = q - shift, pb = pa + 1;
+        const bool va = pa >= 0 && pa < P, vb = pb < P;
+        if (!va && !vb) continue;
+        const int64_t p = va ? pa : pb;
+        int lo = 0, hi = ngt;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= p) lo = mid; else hi = mid;
+        }
+        const uint64_t r = (uint64_t)(p - s_off[lo]);
+        uint32_t R = s_R[lo];
+        uint64_t li, rj;
+        if (r >> 32) {
+            li = r / R;
+            rj = r - li * R;
+        } else {
+            li = (uint32_t)r / R;
+            rj = (uint32_t)r - (uint32_t)li * R;
+        }
+        Pair x, y;
+        x.key = ckey[c0 + lo];
+        x.ws = cws[c0 + lo];
+        x.lp = gpay[s_first[lo] + li];
+        x.rp = gpay[s_rb[lo] + rj];
+        y = x;
+        if (va && vb) {
+            if (pb >= s_off[lo + 1]) {  // the next descriptor: its pair 0
+                ++lo;
+                y.key = ckey[c0 + lo];
+                y.ws = cws[c0 + lo];
+                y.lp = gpay[s_first[lo]];
+                y.rp = gpay[s_rb[lo]];
+            } else if (rj + 1 < R) {
+                y.rp = gpay[s_rb[lo] + rj + 1];
+            } else {
+                y.lp = gpay[s_first[lo] + li + 1];
+                y.rp = gpay[s_rb[lo]];
+            }
+        }
+        if (VEC && va && vb) {
+            *reinterpret_cast<I64x2*>(o.col[0] + pa) = I64x2{x.key, y.key};
+            *reinterpret_cast<I64x2*>(o.col[1] + pa) = I64x2{x.ws, y.ws};
+            *reinterpret_cast<I64x2*>(o.col[2] + pa) = I64x2{x.ws + size, y.ws + size};
+            *reinterpret_cast<I64x2*>(o.col[3] + pa) = I64x2{x.lp, y.lp};
+            *reinterpret_cast<I64x2*>(o.col[4] + pa) = I64x2{x.rp, y.rp};
+        } else {
+            if (va) {
+                o.col[0][pa] = x.key; o.col[1][pa] = x.ws; o.col[2][pa] = x.ws + size;
+                o.col[3][pa] = x.lp; o.col[4][pa] = x.rp;
+            }
+            if (vb) {
+                o.col[0][pb] = y.key; o.col[1][pb] = y.ws; o.col[2][pb] = y.ws + size;
+                o.col[3][pb] = y.lp; o.col[4][pb] = y.rp;
+            }
+        }
+    }
+}
+
+// ---- the stateless core ---------------------------------------------------------------------
+struct Scratch {
+    char* p = nullptr;
+    size_t cap = 0;
+};
+static int scratch_ensure(Scratch& s, size_t need, std::string& why) {
+    if (need <= s.cap) return GW_OK;
+    if (s.p) hipFree(s.p);
+    s.p = nullptr;
+    s.cap = 0;
+    if (hipMalloc((void**)&s.p, need) != hipSuccess) {
+        (void)hipGetLastError();
+        why = "window join: scratch allocation failed";
+        return GW_E_OOM;
+    }
+    s.cap = need;
+    return GW_OK;
+}
+// Carves 256-byte aligned arrays out of one block; with base = nullptr it only adds up.
+struct Carve {
+    char* base;
+    size_t at = 0;
+    template <typename T>
+    T* take(int64_t n) {
+        T* r = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += ((size_t)std::max<int64_t>(n, 1) * sizeof(T) + 255) / 256 * 256;
+        return r;
+    }
+};
+static int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + kJoinThreads - 1) / kJoinThreads, kJoinMaxBlocks)); }
+static int bit_length(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+struct RecArrays {  // by records
+    int64_t* hdr;
+    uint32_t *cnt, *toff;
+    int64_t* blk;
+    void carve(Carve& c, int64_t n) {
+        hdr = c.take<int64_t>(kJoinHdr);
+        cnt = c.take<uint32_t>(n);
+        toff = c.take<uint32_t>(n);
+        blk = c.take<int64_t>(scan_blocks(n) + 1);
+    }
+};
+struct TupArrays {  // by tuples
+    uint64_t *kw0, *kw1, *ord, *ord0, *ord1, *gord;
+    uint32_t *v0, *v1, *src, *gsrc, *head, *hex, *gfirst, *gmid, *ne, *cidx, *cfirst, *crb, *cR;
+    int64_t *gkey, *gpay, *prod, *poff, *coff, *ckey, *cws, *blk;
+    void* sort;
+    void carve(Carve& c, int64_t nt) {
+        kw0 = c.take<uint64_t>(nt); kw1 = c.take<uint64_t>(nt); ord = c.take<uint64_t>(nt);
+        ord0 = c.take<uint64_t>(nt); ord1 = c.take<uint64_t>(nt); gord = c.take<uint64_t>(nt);
+        v0 = c.take<uint32_t>(nt); v1 = c.take<uint32_t>(nt); src = c.take<uint32_t>(nt); gsrc = c.take<uint32_t>(nt);
+        head = c.take<uint32_t>(nt); hex = c.take<uint32_t>(nt); gfirst = c.take<uint32_t>(nt);
+        gmid = c.take<uint32_t>(nt); ne = c.take<uint32_t>(nt); cidx = c.take<uint32_t>(nt);
+        cfirst = c.take<uint32_t>(nt); crb = c.take<uint32_t>(nt); cR = c.take<uint32_t>(nt);
+        gkey = c.take<int64_t>(nt); gpay = c.take<int64_t>(nt); prod = c.take<int64_t>(nt); poff = c.take<int64_t>(nt);
+        coff = c.take<int64_t>(nt + 1); ckey = c.take<int64_t>(nt); cws = c.take<int64_t>(nt);
+        blk = c.take<int64_t>(scan_blocks(nt) + 1);
+        sort = c.take<char>(sort_scratch_bytes(nt));
+    }
+};
+
+// provide(total, out): the caller's output columns for `total` pairs (or an error).
+typedef std::function<int(int64_t, JoinOut&, std::string&)> JoinProvide;
+
+struct JoinTimes {  // HIP events around the expand kernel (scripts/join_bench.py)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+int join_run(const JoinIn& a, const JoinProvide& provide, int64_t* n_pairs, int64_t* n_tuples, hipStream_t s,
+             std::string& why, const JoinTimes* times = nullptr) {
+    static std::mutex mu;
+    static Scratch scr_rec[64], scr_tup[64];
+    *n_pairs = 0;
+    if (n_tuples) *n_tuples = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { why = "window join: no device"; return GW_E_DEVICE; }
+    std::lock_guard<std::mutex> lock(mu);  // every call waits for its launches before it returns
+    auto dev_fail = [&](hipError_t e) {
+        why = std::string("window join: ") + hipGetErrorString(e);
+        return GW_E_DEVICE;
+    };
+    Carve size_r{nullptr};
+    RecArrays R;
+    R.carve(size_r, a.n);
+    int rc = scratch_ensure(scr_rec[dev], size_r.at, why);
+    if (rc) return rc;
+    Carve cr{scr_rec[dev].p};
+    R.carve(cr, a.n);
+    hipLaunchKernelGGL(k_join_hdr_init, dim3(1), dim3(kJoinThreads), 0, s, R.hdr);
+    hipLaunchKernelGGL(k_join_count, dim3(grid_for(a.n)), dim3(kJoinThreads), 0, s, a, R.cnt, R.hdr);
+    hipError_t e = scan_excl<uint32_t, uint32_t>(R.cnt, R.toff, a.n, R.blk, R.hdr + JH_NT, s);
+    int64_t h[kJoinHdr];
+    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return dev_fail(e);
+    if (h[JH_FLAGS] & GW_DF_NO_TS) {
+        why = "Record has Long.MIN_VALUE timestamp (= no timestamp marker)";
+        return GW_E_NO_TIMESTAMP;
+    }
+    if (h[JH_FLAGS] & GW_DF_RANGE) { why = "window join: window bounds overflow int64"; return GW_E_RANGE; }
+    const int64_t nt = h[JH_NT];
+    if (n_tuples) *n_tuples = nt;
+    if (nt > kSortMaxRecords) {
+        why = "window join: more than 2^30 - 1 (record, fired window) tuples in one fire";
+        return GW_E_UNSUPPORTED;
+    }
+    if (nt == 0) {
+        JoinOut none{};
+        return provide(0, none, why);
+    }
+    const int64_t min_start = h[JH_MINS];
+    const uint64_t min_kw = (uint64_t)h[JH_MINK];
+    const int kbits = bit_length((uint64_t)h[JH_MAXK] - min_kw);
+    const int obits = bit_length(((uint64_t)h[JH_MAXS] - (uint64_t)min_start) / (uint64_t)a.g.slide);
+    Carve size_t_{nullptr};
+    TupArrays T;
+    T.carve(size_t_, nt);
+    if ((rc = scratch_ensure(scr_tup[dev], size_t_.at, why))) return rc;
+    Carve ct{scr_tup[dev].p};
+    T.carve(ct, nt);
+    const int gt = grid_for(nt);
+    hipLaunchKernelGGL(k_join_emit, dim3(grid_for(a.n)), dim3(kJoinThreads), 0, s, a, R.toff, min_start, min_kw, T.kw0, T.ord,
+                       T.src);
+    if ((e = hipGetLastError()) != hipSuccess) return dev_fail(e);
+    // by key word, then by window ordinal: both stable, so a group keeps left before right and
+    // each side its arrival order
+    int alt = 0;
+    if ((e = sort_pairs_u64(T.kw0, T.v0, T.kw1, T.v1, nt, 0, kbits, T.sort, s, &alt, true)) != hipSuccess) return dev_fail(e);
+    uint32_t* perm = alt ? T.v1 : T.v0;
+    if (obits > 0) {
+        uint32_t* other = alt ? T.v0 : T.v1;
+        hipLaunchKernelGGL(k_join_gather_ord, dim3(gt), dim3(kJoinThreads), 0, s, nt, perm, T.ord, T.ord0);
+        if ((e = sort_pairs_u64(T.ord0, perm, T.ord1, other, nt, 0, obits, T.sort, s, &alt, false)) != hipSuccess)
+            return dev_fail(e);
+        if (alt) perm = other;
+    }
+    hipLaunchKernelGGL(k_join_gather, dim3(gt), dim3(kJoinThreads), 0, s, a, nt, perm, T.ord, T.src, T.gkey, T.gord, T.gsrc,
+                       T.gpay);
+    hipLaunchKernelGGL(k_join_heads, dim3(gt), dim3(kJoinThreads), 0, s, nt, T.gkey, T.gord, T.head);
+    if ((e = scan_excl<uint32_t, uint32_t>(T.head, T.hex, nt, T.blk, R.hdr + JH_NG, s)) != hipSuccess) return dev_fail(e);
+    if ((e = hipMemsetAsync(T.gmid, 0xFF, (size_t)nt * 4, s)) != hipSuccess) return dev_fail(e);
+    hipLaunchKernelGGL(k_join_group_fill, dim3(gt), dim3(kJoinThreads), 0, s, nt, T.head, T.hex, T.gsrc, T.gfirst, T.gmid);
+    hipLaunchKernelGGL(k_join_group_prod, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, T.prod, T.ne);
+    if ((e = scan_excl<int64_t, int64_t>(T.prod, T.poff, nt, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return dev_fail(e);
+    if ((e = scan_excl<uint32_t, uint32_t>(T.ne, T.cidx, nt, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return dev_fail(e);
+    hipLaunchKernelGGL(k_join_compact, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, T.prod, T.poff, T.cidx,
+                       T.gkey, T.gord, min_start, a.g.slide, T.coff, T.cfirst, T.crb, T.cR, T.ckey, T.cws);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return dev_fail(e);
+    const int64_t total = h[JH_TOTAL], nc = h[JH_NC];
+    if (total > INT64_MAX / 40) { why = "window join: the pairs of one fire exceed int64 bytes"; return GW_E_RANGE; }
+    *n_pairs = total;
+    JoinOut out{};
+    if ((rc = provide(total, out, why))) return rc;
+    if (total == 0) return GW_OK;
+    // two pairs per 16-byte store need the five columns at one alignment
+    int par[5];
+    for (int c = 0; c < 5; ++c) par[c] = (int)(((uintptr_t)out.col[c] >> 3) & 1);
+    const bool vec = par[0] == par[1] && par[0] == par[2] && par[0] == par[3] && par[0] == par[4] &&
+                     !((uintptr_t)out.col[0] & 7);
+    const int shift = vec ? par[0] : 0;
+    const int64_t nblk = (total + shift + kExpTile - 1) / kExpTile;
+    if (times) (void)hipEventRecord(times->e0, s);
+    if (vec)
+        hipLaunchKernelGGL(k_join_expand<true>, dim3((unsigned)nblk), dim3(kJoinThreads), 0, s, total, shift, nc, T.coff,
+                           T.cfirst, T.crb, T.cR, T.ckey, T.cws, T.gpay, a.g.size, out);
+    else
+        hipLaunchKernelGGL(k_join_expand<false>, dim3((unsigned)nblk), dim3(kJoinThreads), 0, s, total, shift, nc, T.coff,
+                           T.cfirst, T.crb, T.cR, T.ckey, T.cws, T.gpay, a.g.size, out);
+    e = hipGetLastError();
+    if (times) (void)hipEventRecord(times->e1, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the scratch is free for the next call
+    if (e != hipSuccess) return dev_fail(e);
+    return GW_OK;
+}
+
+// ---- operator state: late filter and stable compaction -------------------------------------
+// keep[i] = 1 for the records that stay: at ingest those with a window still open at wm (the
+// others are late, counted in hdr[JH_LATE]); after a fire the same test at the new watermark.
+__global__ void __launch_bounds__(kJoinThreads) k_join_filter(int64_t n, const int64_t* __restrict__ ts, JoinGeom g,
+                                                              int64_t wm, uint32_t* keep, int64_t* hdr) {
+    using ull = unsigned long long;
+    __shared__ uint64_t s_late[4], s_flags[4];
+    uint64_t late = 0, flags = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads) {
+        int64_t ls;
+        int nw;
+        const unsigned f = join_windows(g, ts[i], ls, nw);
+        flags |= f;
+        const bool k = !f && ls + (g.size - 1) > wm;
+        late += !f && !k;
+        keep[i] = k;
+    }
+    late = wave_sum(late);
+    flags = wave_ior(flags);
+    if (__lane_id() == 0) {
+        s_late[threadIdx.x >> 6] = late;
+        s_flags[threadIdx.x >> 6] = flags;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 4; ++w) {
+        late += s_late[w];
+        flags |= s_flags[w];
+    }
+    if (late) atomicAdd((ull*)&hdr[JH_LATE], (ull)late);
+    if (flags) atomicOr((ull*)&hdr[JH_FLAGS], (ull)flags);
+}
+struct Cols3 {
+    const int64_t* in[3];
+    int64_t* out[3];
+};
+__global__ void __launch_bounds__(kJoinThreads) k_join_append(int64_t n, const uint32_t* __restrict__ keep,
+                                                              const uint32_t* __restrict__ off, Cols3 c) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads) {
+        if (!keep[i]) continue;
+        const uint32_t d = off[i];
+        c.out[0][d] = c.in[0][i];
+        c.out[1][d] = c.in[1][i];
+        c.out[2][d] = c.in[2][i];
+    }
+}
+
+}  // namespace gw
+
+using namespace gw;
+
+// ---- the operator ---------------------------------------------------------------------------
+struct gw_join {
+    gw_join_config cfg{};
+    JoinGeom g{};
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    DevCols<3> log[2], alt, stage;
+    int64_t n_log[2] = {0, 0};
+    DevCols<5> out;
+    int64_t out_from = 0, pending = 0;
+    DevBuf<char> scr;
+    int64_t wm = INT64_MIN, late = 0, max_batch = 0;
+    bool failed = false;
+    std::string err;
+    gw_join_stats st{};
+
+    int fail(int rc, const char* fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        err = buf;
+        if (rc != GW_E_OUTPUT_FULL && rc != GW_E_INVALID) failed = true;
+        return rc;
+    }
+    int dev_fail(hipError_t e) { return fail(GW_E_DEVICE, "window join: %s", hipGetErrorString(e)); }
+
+    // hdr, keep, off and the scan's block sums for n records
+    int filter_scratch(int64_t n, RecArrays& R) {
+        Carve sz{nullptr};
+        R.carve(sz, n);
+        if (scr.reserve_discard((int64_t)sz.at) != hipSuccess) return fail(GW_E_OOM, "window join: out of device memory");
+        Carve c{scr.p};
+        R.carve(c, n);
+        return GW_OK;
+    }
+    // The records of (key, ts, pay)[0..n) with a window open at `w`, in order, to dst columns
+    // from row `at`; *kept and *dropped their numbers.  One synchronisation.
+    int filter_into(int64_t n, const int64_t* key, const int64_t* ts, const int64_t* pay, int64_t w, int64_t* const* dst,
+                    int64_t at, int64_t* kept, int64_t* dropped) {
+        RecArrays R;
+        int rc = filter_scratch(n, R);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_join_hdr_init, dim3(1), dim3(kJoinThreads), 0, stream, R.hdr);
+        hipLaunchKernelGGL(k_join_filter, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, ts, g, w, R.cnt, R.hdr);
+        hipError_t e = scan_excl<uint32_t, uint32_t>(R.cnt, R.toff, n, R.blk, R.hdr + JH_KEPT, stream);
+        if (e != hipSuccess) return dev_fail(e);
+        Cols3 c{{key, ts, pay}, {dst[0] + at, dst[1] + at, dst[2] + at}};
+        hipLaunchKernelGGL(k_join_append, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, R.cnt, R.toff, c);
+        int64_t h[kJoinHdr];
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof h, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return dev_fail(e);
+        if (h[JH_FLAGS] & GW_DF_NO_TS)
+            return fail(GW_E_NO_TIMESTAMP, "Record has Long.MIN_VALUE timestamp (= no timestamp marker)");
+        if (h[JH_FLAGS] & GW_DF_RANGE) return fail(GW_E_RANGE, "window join: window bounds overflow int64");
+        *kept = h[JH_KEPT];
+        *dropped = h[JH_LATE];
+        return GW_OK;
+    }
+    int reserve_log(int side, int64_t need) {
+        if (need <= log[side].cap) return GW_OK;
+        const int64_t cap = std::max<int64_t>(need, 2 * log[side].cap);
+        if (log[side].reserve_keep(cap, 0, n_log[side], stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(GW_E_OOM, "window join: out of device memory growing the %s log", side ? "right" : "left");
+        }
+        ++st.log_growths;
+        return GW_OK;
+    }
+    // device columns, already ordered behind their producer
+    int ingest_cols(int side, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* pay) {
+        for (int64_t at = 0; at < n; at += max_batch) {
+            const int64_t m = std::min(max_batch, n - at);
+            int rc = reserve_log(side, n_log[side] + m);
+            if (rc) return rc;
+            int64_t kept = 0, dropped = 0;
+            if ((rc = filter_into(m, key + at, ts + at, pay + at, wm, log[side].col, n_log[side], &kept, &dropped))) return rc;
+            n_log[side] += kept;
+            late += dropped;
+        }
+        return GW_OK;
+    }
+    int reserve_out(int64_t more) {
+        if (out_from + pending + more <= out.cap) return GW_OK;
+        const int64_t cap = std::max<int64_t>(pending + more, 2 * out.cap);
+        if (out.reserve_keep(cap, out_from, pending, stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(GW_E_OOM, "window join: out of device memory for %lld pending pairs", (long long)(pending + more));
+        }
+        out_from = 0;
+        return GW_OK;
+    }
+    int advance(int64_t w, int64_t* pairs_fired) {
+        if (pairs_fired) *pairs_fired = 0;
+        if (w <= wm) return GW_OK;  // a watermark that does not advance is ignored
+        int64_t fired = 0, tuples = 0;
+        if (n_log[0] > 0 && n_log[1] > 0) {
+            JoinIn a{};
+            for (int sd = 0; sd < 2; ++sd) {
+                a.key[sd] = log[sd][0];
+                a.ts[sd] = log[sd][1];
+                a.pay[sd] = log[sd][2];
+            }
+            a.n_l = n_log[0];
+            a.n = n_log[0] + n_log[1];
+            a.g = g;
+            a.w0 = wm;
+            a.w1 = w;
+            std::string why;
+            const int rc = join_run(a, [&](int64_t total, JoinOut& o, std::string&) {
+                int r = reserve_out(total);
+                if (r) return r;
+                for (int c = 0; c < 5; ++c) o.col[c] = out[c] + out_from + pending;
+                return (int)GW_OK;
+            }, &fired, &tuples, stream, why);
+            if (rc) return failed ? rc : fail(rc, "%s", why.c_str());
+            pending += fired;
+        }
+        // the records whose last window has fired leave the logs
+        for (int sd = 0; sd < 2; ++sd) {
+            if (n_log[sd] == 0) continue;
+            if (alt.cap < n_log[sd] && alt.reserve_keep(std::max(n_log[sd], log[sd].cap), 0, 0, stream) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(GW_E_OOM, "window join: out of device memory compacting a log");
+            }
+            int64_t kept = 0, dropped = 0;
+            const int rc = filter_into(n_log[sd], log[sd][0], log[sd][1], log[sd][2], w, alt.col, 0, &kept, &dropped);
+            if (rc) return rc;
+            std::swap(log[sd], alt);
+            n_log[sd] = kept;
+        }
+        wm = w;
+        ++st.fires;
+        st.pairs_fired += fired;
+        st.last_fire_tuples = tuples;
+        if (pairs_fired) *pairs_fired = fired;
+        return GW_OK;
+    }
+};
+
+namespace {
+
+int join_geom(int64_t size, int64_t slide, int64_t offset, JoinGeom& g, std::string& why) {
+    auto ab = [](int64_t v) { return v < 0 ? -v : v; };
+    if (size <= 0 || slide <= 0 || offset == INT64_MIN || ab(offset) >= slide) {
+        why = "window join: parameters must satisfy size > 0, slide > 0 and abs(offset) < slide";
+        return GW_E_INVALID;
+    }
+    if ((size - 1) / slide + 1 > GW_JOIN_MAX_WINDOWS) {
+        why = "window join: more than GW_JOIN_MAX_WINDOWS (64) windows per record";
+        return GW_E_UNSUPPORTED;
+    }
+    g = JoinGeom{size, slide, offset};
+    return GW_OK;
+}
+
+int join_args(int64_t n_l, int64_t n_r, int64_t size, int64_t slide, int64_t offset, int64_t cap, const int64_t* n_out,
+              JoinGeom& g, std::string& why) {
+    if (!n_out || n_l < 0 || n_r < 0 || cap < 0) { why = "window join: bad argument"; return GW_E_INVALID; }
+    return join_geom(size, slide, offset, g, why);
+}
+
+}  // namespace
+
+extern "C" {
+
+// gw_window_join_device, with the expand kernel's time in *expand_ms when that is not null.
+static int join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay, int64_t n_r,
+                       const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay, int64_t size, int64_t slide,
+                       int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out, int64_t* d_start_out,
+                       int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out, int64_t cap, int64_t* n_out,
+                       void* stream, double* expand_ms) {
+    JoinGeom g;
+    std::string why;
+    int rc = join_args(n_l, n_r, size, slide, offset, cap, n_out, g, why);
+    if (rc) { set_last_error(why); return rc; }
+    *n_out = 0;
+    if (expand_ms) *expand_ms = 0;
+    if (n_l == 0 || n_r == 0 || w1 <= w0) return GW_OK;
+    if (!d_lkey || !d_lts || !d_lpay || !d_rkey || !d_rts || !d_rpay ||
+        (cap > 0 && (!d_key_out || !d_start_out || !d_end_out || !d_lpay_out || !d_rpay_out))) {
+        set_last_error("window join: null column");
+        return GW_E_INVALID;
+    }
+    if (n_l > INT32_MAX || n_r > INT32_MAX) {
+        set_last_error("window join: more than 2^31 - 1 records on one side");
+        return GW_E_UNSUPPORTED;
+    }
+    JoinTimes t;
+    if (expand_ms && (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess)) {
+        if (t.e0) (void)hipEventDestroy(t.e0);
+        set_last_error("window join: hipEventCreate");
+        return GW_E_DEVICE;
+    }
+    JoinIn a{{d_lkey, d_rkey}, {d_lts, d_rts}, {d_lpay, d_rpay}, n_l, n_l + n_r, g, w0, w1};
+    int64_t pairs = 0;
+    rc = join_run(a, [&](int64_t total, JoinOut& o, std::string& w) {
+        *n_out = total;
+        if (total > cap) { w = "window join: output arrays too small"; return (int)GW_E_OUTPUT_FULL; }
+        o = JoinOut{{d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out}};
+        return (int)GW_OK;
+    }, &pairs, nullptr, (hipStream_t)stream, why, expand_ms ? &t : nullptr);
+    if (expand_ms) {
+        float ms = 0;
+        if (rc == GW_OK && pairs > 0 && hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) *expand_ms = ms;
+        (void)hipEventDestroy(t.e0);
+        (void)hipEventDestroy(t.e1);
+    }
+    if (rc) set_last_error(why);
+    return rc;
+}
+
+int gw_window_join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay, int64_t n_r,
+                          const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay, int64_t size, int64_t slide,
+                          int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out, int64_t* d_start_out,
+                          int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out, int64_t cap, int64_t* n_out,
+                          void* stream) {
+    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, d_key_out,
+                       d_start_out, d_end_out, d_lpay_out, d_rpay_out, cap, n_out, stream, nullptr);
+}
+
+int gw_window_join_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out,
+                                int64_t* d_start_out, int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out,
+                                int64_t cap, int64_t* n_out, void* stream, double* expand_ms) {
+    if (!expand_ms) { set_last_error("window join: null expand_ms"); return GW_E_INVALID; }
+    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, d_key_out,
+                       d_start_out, d_end_out, d_lpay_out, d_rpay_out, cap, n_out, stream, expand_ms);
+}
+
+int gw_window_join_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                        const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
+                        int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out, int64_t* end_out,
+                        int64_t* lpay_out, int64_t* rpay_out, int64_t cap, int64_t* n_out) {
+    JoinGeom g;
+    std::string why;
+    int rc = join_args(n_l, n_r, size, slide, offset, cap, n_out, g, why);
+    if (rc) { set_last_error(why); return rc; }
+    *n_out = 0;
+    if (n_l == 0 || n_r == 0 || w1 <= w0) return GW_OK;
+    if (!lkey || !lts || !lpay || !rkey || !rts || !rpay ||
+        (cap > 0 && (!key_out || !start_out || !end_out || !lpay_out || !rpay_out))) {
+        set_last_error("window join: null column");
+        return GW_E_INVALID;
+    }
+    try {
+        struct Tup {
+            int64_t start, key, pay;
+            int side;
+        };
+        std::vector<Tup> t;
+        const int64_t* keys[2] = {lkey, rkey};
+        const int64_t* tss[2] = {lts, rts};
+        const int64_t* pays[2] = {lpay, rpay};
+        const int64_t ns[2] = {n_l, n_r};
+        for (int side = 0; side < 2; ++side)
+            for (int64_t i = 0; i < ns[side]; ++i) {
+                int64_t ls;
+                int nw;
+                const unsigned f = join_windows(g, tss[side][i], ls, nw);
+                if (f & GW_DF_NO_TS) {
+                    set_last_error("Record has Long.MIN_VALUE timestamp (= no timestamp marker)");
+                    return GW_E_NO_TIMESTAMP;
+                }
+                if (f) { set_last_error("window join: window bounds overflow int64"); return GW_E_RANGE; }
+                uint64_t m = join_fired(g, ls, nw, w0, w1);
+                for (int k = 0; m; ++k, m >>= 1)
+                    if (m & 1) t.push_back({ls - (int64_t)k * g.slide, keys[side][i], pays[side][i], side});
+            }
+        if ((int64_t)t.size() > kSortMaxRecords) {
+            set_last_error("window join: more than 2^30 - 1 (record, fired window) tuples in one fire");
+            return GW_E_UNSUPPORTED;
+        }
+        // left tuples were made first, each side in arrival order: stability keeps both
+        std::stable_sort(t.begin(), t.end(), [](const Tup& x, const Tup& y) {
+            return x.start != y.start ? x.start < y.start : x.key < y.key;
+        });
+        const size_t n = t.size();
+        __int128 total = 0;
+        for (size_t i = 0; i < n;) {
+            size_t j = i, l = 0;
+            for (; j < n && t[j].start == t[i].start && t[j].key == t[i].key; ++j) l += t[j].side == 0;
+            total += (__int128)l * (__int128)(j - i - l);
+            i = j;
+        }
+        if (total > (__int128)(INT64_MAX / 40)) {
+            set_last_error("window join: the pairs of one fire exceed int64 bytes");
+            return GW_E_RANGE;
+        }
+        *n_out = (int64_t)total;
+        if ((int64_t)total > cap) { set_last_error("window join: output arrays too small"); return GW_E_OUTPUT_FULL; }
+        int64_t o = 0;
+        for (size_t i = 0; i < n;) {
+            size_t j = i, l = 0;
+            for (; j < n && t[j].start == t[i].start && t[j].key == t[i].key; ++j) l += t[j].side == 0;
+            for (size_t x = i; x < i + l; ++x)
+                for (size_t y = i + l; y < j; ++y, ++o) {
+                    key_out[o] = t[i].key;
+                    start_out[o] = t[i].start;
+                    end_out[o] = t[i].start + g.size;
+                    lpay_out[o] = t[x].pay;
+                    rpay_out[o] = t[y].pay;
+                }
+            i = j;
+        }
+    } catch (const std::bad_alloc&) {
+        set_last_error("window join: out of host memory");
+        return GW_E_OOM;
+    }
+    return GW_OK;
+}
+
+int gw_join_create(const gw_join_config* cfg, gw_join** out) {
+    if (!cfg || !out) { set_last_error("gw_join_create: null argument"); return GW_E_INVALID; }
+    *out = nullptr;
+    if (cfg->assigner != GW_TUMBLING && cfg->assigner != GW_SLIDING) {
+        set_last_error("window join: only tumbling and sliding event-time windows (no session or count windows)");
+        return GW_E_UNSUPPORTED;
+    }
+    JoinGeom g;
+    std::string why;
+    int rc = join_geom(cfg->size, cfg->assigner == GW_TUMBLING ? cfg->size : cfg->slide, cfg->offset, g, why);
+    if (rc) { set_last_error(why); return rc; }
+    if (cfg->capacity_hint < 0 || cfg->max_batch < 0) { set_last_error("gw_join_create: negative capacity"); return GW_E_INVALID; }
+    gw_join* h = new (std::nothrow) gw_join();
+    if (!h) { set_last_error("gw_join_create: out of host memory"); return GW_E_OOM; }
+    auto bail = [&](int code, const std::string& msg) {
+        set_last_error(msg);
+        gw_join_destroy(h);
+        return code;
+    };
+    h->cfg = *cfg;
+    h->g = g;
+    h->max_batch = cfg->max_batch > 0 ? std::min<int64_t>(cfg->max_batch, (int64_t)1 << 30) : (int64_t)1 << 22;
+    hipError_t e = hipSetDevice(cfg->device);
+    if (e != hipSuccess) return bail(GW_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
+        return bail(GW_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    if ((e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming)) != hipSuccess)
+        return bail(GW_E_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    const int64_t cap0 = std::max<int64_t>(cfg->capacity_hint, 16);
+    for (int sd = 0; sd < 2; ++sd)
+        if (h->log[sd].reserve_keep(cap0, 0, 0, h->stream) != hipSuccess) return bail(GW_E_OOM, "window join: out of device memory");
+    *out = h;
+    return GW_OK;
+}
+
+int gw_join_destroy(gw_join* h) {
+    if (!h) return GW_OK;
+    hipSetDevice(h->cfg.device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->ev_in) hipEventDestroy(h->ev_in);
+    if (h->ev_out) hipEventDestroy(h->ev_out);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+    return GW_OK;
+}
+
+const char* gw_join_last_error(const gw_join* h) { return h ? h->err.c_str() : gw_last_error(nullptr); }
+
+#define JOIN_ENTER(h)                                                                     \
+    if (!(h)) return GW_E_INVALID;                                                        \
+    if ((h)->failed) return GW_E_STATE;                                                   \
+    hipSetDevice((h)->cfg.device)
+
+int gw_join_ingest_device(gw_join* h, int32_t side, int64_t n, const int64_t* d_key, const int64_t* d_ts,
+                          const int64_t* d_payload, void* stream) {
+    JOIN_ENTER(h);
+    if ((side != 0 && side != 1) || n < 0 || (n > 0 && (!d_key || !d_ts || !d_payload)))
+        return h->fail(GW_E_INVALID, "gw_join_ingest_device: bad side or null column");
+    if (n + h->n_log[side] > INT32_MAX) return h->fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
+    hipStream_t ps = (hipStream_t)stream;
+    if (ps != h->stream) {
+        hipEventRecord(h->ev_in, ps);
+        hipStreamWaitEvent(h->stream, h->ev_in, 0);
+    }
+    if (n == 0) return GW_OK;
+    const int rc = h->ingest_cols(side, n, d_key, d_ts, d_payload);
+    if (ps != h->stream) {
+        hipEventRecord(h->ev_out, h->stream);
+        hipStreamWaitEvent(ps, h->ev_out, 0);
+    }
+    return rc;
+}
+
+int gw_join_ingest(gw_join* h, int32_t side, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* payload) {
+    JOIN_ENTER(h);
+    if ((side != 0 && side != 1) || n < 0 || (n > 0 && (!key || !ts || !payload)))
+        return h->fail(GW_E_INVALID, "gw_join_ingest: bad side or null column");
+    if (n + h->n_log[side] > INT32_MAX) return h->fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
+    for (int64_t at = 0; at < n; at += h->max_batch) {
+        const int64_t m = std::min(h->max_batch, n - at);
+        if (h->stage.cap < m && h->stage.reserve_keep(m, 0, 0, h->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return h->fail(GW_E_OOM, "window join: out of device memory staging a batch");
+        }
+        const int64_t* src[3] = {key + at, ts + at, payload + at};
+        for (int c = 0; c < 3; ++c) {
+            const hipError_t e = hipMemcpyAsync(h->stage[c], src[c], (size_t)m * 8, hipMemcpyHostToDevice, h->stream);
+            if (e != hipSuccess) return h->dev_fail(e);
+        }
+        // (ingest_cols waits for the stream, so the host columns are free when this returns)
+        const int rc = h->ingest_cols(side, m, h->stage[0], h->stage[1], h->stage[2]);
+        if (rc) return rc;
+    }
+    return GW_OK;
+}
+
+int gw_join_advance_watermark(gw_join* h, int64_t watermark, int64_t* pairs_fired) {
+    JOIN_ENTER(h);
+    return h->advance(watermark, pairs_fired);
+}
+
+int gw_join_end_input(gw_join* h, int64_t* pairs_fired) {
+    JOIN_ENTER(h);
+    return h->advance(INT64_MAX, pairs_fired);
+}
+
+int gw_join_pending(gw_join* h, int64_t* n) {
+    JOIN_ENTER(h);
+    if (!n) return h->fail(GW_E_INVALID, "gw_join_pending: null argument");
+    *n = h->pending;
+    return GW_OK;
+}
+
+int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay, int64_t cap,
+                  int64_t* n) {
+    JOIN_ENTER(h);
+    if (!n || cap < 0 || (cap > 0 && (!key || !start || !end || !lpay || !rpay)))
+        return h->fail(GW_E_INVALID, "gw_join_drain: bad argument");
+    const int64_t m = std::min(cap, h->pending);
+    *n = m;
+    int64_t* dst[5] = {key, start, end, lpay, rpay};
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < 5 && m > 0 && e == hipSuccess; ++c)
+        e = hipMemcpyAsync(dst[c], h->out[c] + h->out_from, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return h->dev_fail(e);
+    h->out_from += m;
+    h->pending -= m;
+    if (h->pending == 0) h->out_from = 0;
+    return h->pending > 0 ? GW_E_OUTPUT_FULL : GW_OK;
+}
+
+int gw_join_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                        const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n) {
+    JOIN_ENTER(h);
+    if (!d_key || !d_start || !d_end || !d_lpay || !d_rpay || !n) return h->fail(GW_E_INVALID, "gw_join_rows_device: null argument");
+    const int64_t** dst[5] = {d_key, d_start, d_end, d_lpay, d_rpay};
+    for (int c = 0; c < 5; ++c) *dst[c] = h->pending ? h->out[c] + h->out_from : nullptr;
+    *n = h->pending;
+    return GW_OK;
+}
+
+int gw_join_clear_rows(gw_join* h) {
+    JOIN_ENTER(h);
+    h->pending = 0;
+    h->out_from = 0;
+    return GW_OK;
+}
+
+int64_t gw_join_late_dropped(const gw_join* h) { return h ? h->late : 0; }
+
+int gw_join_get_stats(const gw_join* h, gw_join_stats* out) {
+    if (!h || !out) return GW_E_INVALID;
+    *out = h->st;
+    out->live_left = h->n_log[0];
+    out->live_right = h->n_log[1];
+    out->log_capacity_left = h->log[0].cap;
+    out->log_capacity_right = h->log[1].cap;
+    return GW_OK;
+}
+
+void* gw_join_stream(gw_join* h) { return h ? (void*)h->stream : nullptr; }
+
+}  // extern "C"

@@ -444,6 +444,11 @@ int top_n_run(int64_t n, const int64_t* d_key, const int64_t* d_start, const int
               int top, int mode, int64_t* key_out, int64_t* start_out, int64_t* end_out, int64_t* res_out,
               int64_t* rows_out, int64_t cap, int64_t* n_out, bool host_out, hipStream_t s, std::string& why);
 
+// gw_join.hip: the event-time window join (gpuwin.h gw_window_join_*, gw_join_*).  The file holds
+// its kernels, the stateless core and the gw_join operator with its C entry points; what it needs
+// from the runtime is the thread's error text behind gw_last_error(NULL) (gw_runtime.cpp).
+void set_last_error(const std::string& why);
+
 // Key -> Java hashCode of the keys a handle was fed with a key_hash column (String,
 // Integer, ... keys mapped to int64 ids by the caller).  The heap backend files a key's
 // state under the key group of key.hashCode() (KeyGroupRangeAssignment.java:63-66), so a

@@ -2635,6 +2635,10 @@ struct gw_handle {
     }
 };
 
+namespace gw {
+void set_last_error(const std::string& why) { g_create_error = why; }
+}  // namespace gw
+
 // ------------------------------------------------------------------------- ABI
 extern "C" {
 

@@ -329,6 +329,67 @@ def top_n_host(key, start, end, result, top: int, smallest: bool = False, f64: b
     return k, s, e, (r.view(np.float64) if is_f else r), w
 
 
+def _join_geometry(assigner: WindowAssigner):
+    """(assigner id, size, slide, offset) of a window join's assigner; session and count windows
+    raise as an unsupported configuration does (GW_E_UNSUPPORTED)."""
+    a = assigner.config()
+    if a["assigner"] not in ("tumbling", "sliding"):
+        raise N.GpuWinError(N.GW_E_UNSUPPORTED,
+                            "window join: only tumbling and sliding event-time windows (no session or count windows)")
+    size = a["size"]
+    return N.ASSIGNERS[a["assigner"]], size, a.get("slide", size) if a["assigner"] == "sliding" else size, a.get("offset", 0)
+
+
+def window_join_device(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner, w0: int = LONG_MIN,
+                       w1: int = LONG_MAX, stream=None):
+    """gw_window_join_device over torch device tensors (int64): the left and right records in
+    arrival order, the windows firing for a watermark going from w0 to w1.  Returns device tensors
+    (key, start, end, left payload, right payload): per fired (window, key) the cross product of
+    the two sides, windows by ascending end, keys ascending, left-major in arrival order -- the
+    window join of Nexmark Q8.  Waits on `stream` (default: torch's current)."""
+    import torch
+    _, size, slide, offset = _join_geometry(assigner)
+    if stream is None:
+        stream = torch.cuda.current_stream(lkey.device).cuda_stream
+    n_out = ctypes.c_int64(0)
+    cap = max(lkey.numel(), rkey.numel(), 1)
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    while True:
+        out = [torch.empty(cap, dtype=torch.int64, device=lkey.device) for _ in range(5)]
+        rc = N.lib().gw_window_join_device(lkey.numel(), P(lkey), P(lts), P(lpay), rkey.numel(), P(rkey), P(rts), P(rpay),
+                                           size, slide, offset, int(w0), int(w1), *[o.data_ptr() for o in out], cap,
+                                           ctypes.byref(n_out), ctypes.c_void_p(stream) if stream else None)
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    return tuple(o[:n_out.value] for o in out)
+
+
+def window_join_host(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner, w0: int = LONG_MIN,
+                     w1: int = LONG_MAX):
+    """gw_window_join_host over numpy columns: the contract of window_join_device as plain host
+    code (no device), for a fire of a few records."""
+    _, size, slide, offset = _join_geometry(assigner)
+    cols = [np.ascontiguousarray(x, dtype=np.int64) for x in (lkey, lts, lpay, rkey, rts, rpay)]
+    if not (len(cols[0]) == len(cols[1]) == len(cols[2]) and len(cols[3]) == len(cols[4]) == len(cols[5])):
+        raise ValueError("column lengths differ")
+    n_out = ctypes.c_int64(0)
+    cap = max(len(cols[0]), len(cols[3]), 1)
+    while True:
+        out = [np.empty(cap, np.int64) for _ in range(5)]
+        rc = N.lib().gw_window_join_host(len(cols[0]), *[_ptr(c) for c in cols[:3]], len(cols[3]),
+                                         *[_ptr(c) for c in cols[3:]], size, slide, offset, int(w0), int(w1),
+                                         *[_ptr(o) for o in out], cap, ctypes.byref(n_out))
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    return tuple(o[:n_out.value] for o in out)
+
+
 # ------------------------------------------------------------------------ operator
 class StatusWatermarkValve:
     """The valve of an input gate with n channels (gw_valve; host code, no device): feed it each
@@ -1095,6 +1156,207 @@ class GpuWindowOperator:
 
 
 # -------------------------------------------------------------- DataStream surface
+class GpuWindowJoinOperator:
+    """Event-time window join of two keyed streams on one MI355X (gw_join): Flink's
+    stream.join(other).where().equalTo().window(assigner).apply(), i.e. union -> keyBy ->
+    WindowOperator with ListState -> JoinCoGroupFunction.  Records are (key, ts, payload) int64
+    columns per side (payload: the element as the caller numbers or packs it); a fire leaves
+    (key, start, end, left payload, right payload) pairs, windows by ascending end, keys ascending,
+    left-major in arrival order.  Tumbling and sliding event-time windows, allowed lateness 0."""
+
+    LEFT, RIGHT = N.JOIN_LEFT, N.JOIN_RIGHT
+
+    def __init__(self, assigner: WindowAssigner, device: int = 0, capacity_hint: int = 0, max_batch: int = 0):
+        self.assigner = assigner
+        c = N.GwJoinConfig()
+        c.assigner, c.size, c.slide, c.offset = _join_geometry(assigner)
+        c.device, c.capacity_hint, c.max_batch = device, capacity_hint, max_batch
+        self.cfg = c
+        self._h = None
+
+    def open(self):
+        h = ctypes.c_void_p()
+        rc = N.lib().gw_join_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc == N.GW_E_INVALID:
+            raise ValueError(N.lib().gw_last_error(None).decode())
+        N.check(rc, None)
+        self._h = h
+        return self
+
+    def close(self):
+        if self._h:
+            N.lib().gw_join_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self.open() if self._h is None else self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc != N.GW_OK:
+            msg = N.lib().gw_join_last_error(self._h)
+            raise N.GpuWinError(rc, msg.decode() if msg else "")
+        return rc
+
+    def process_batch(self, side: int, keys, ts, payload):
+        keys, ts, payload = (np.ascontiguousarray(x, dtype=np.int64) for x in (keys, ts, payload))
+        if not (len(keys) == len(ts) == len(payload)):
+            raise ValueError("column lengths differ")
+        self._check(N.lib().gw_join_ingest(self._h, int(side), len(keys), _ptr(keys), _ptr(ts), _ptr(payload)))
+
+    def process_batch_device(self, side: int, keys, ts, payload, stream=None):
+        """Columns already in HBM (torch int64 tensors), produced on `stream` (default: torch's
+        current): the operator reads them behind that stream's work, and the stream waits for
+        the reads."""
+        if not (keys.numel() == ts.numel() == payload.numel()):
+            raise ValueError("column lengths differ")
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(keys.device).cuda_stream
+        P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+        self._check(N.lib().gw_join_ingest_device(self._h, int(side), keys.numel(), P(keys), P(ts), P(payload),
+                                                  ctypes.c_void_p(stream) if stream else None))
+
+    def advance_watermark(self, wm: int) -> int:
+        fired = ctypes.c_int64(0)
+        self._check(N.lib().gw_join_advance_watermark(self._h, int(wm), ctypes.byref(fired)))
+        return fired.value
+
+    def end_input(self) -> int:
+        fired = ctypes.c_int64(0)
+        self._check(N.lib().gw_join_end_input(self._h, ctypes.byref(fired)))
+        return fired.value
+
+    def pending(self) -> int:
+        n = ctypes.c_int64(0)
+        self._check(N.lib().gw_join_pending(self._h, ctypes.byref(n)))
+        return n.value
+
+    def drain(self, cap: Optional[int] = None):
+        """All pending pairs as numpy (key, start, end, left payload, right payload), copied cap
+        pairs per call (default: all at once)."""
+        n = self.pending()
+        out = [np.empty(n, np.int64) for _ in range(5)]
+        step = n if cap is None else max(1, int(cap))
+        at = 0
+        got = ctypes.c_int64(0)
+        while at < n:
+            rc = N.lib().gw_join_drain(self._h, *[ctypes.c_void_p(o.ctypes.data + 8 * at) for o in out], step,
+                                       ctypes.byref(got))
+            if rc != N.GW_E_OUTPUT_FULL:
+                self._check(rc)
+            at += got.value
+            if rc == N.GW_OK:
+                break
+        assert at == n
+        return tuple(out)
+
+    def rows_device(self):
+        """Zero-copy view of the pending pairs: five device pointers and their number."""
+        p = [ctypes.c_void_p() for _ in range(5)]
+        n = ctypes.c_int64(0)
+        self._check(N.lib().gw_join_rows_device(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
+        return [x.value for x in p], n.value
+
+    def clear_rows(self):
+        self._check(N.lib().gw_join_clear_rows(self._h))
+
+    def num_late_records_dropped(self) -> int:
+        return int(N.lib().gw_join_late_dropped(self._h))
+
+    def stats(self) -> dict:
+        s = N.GwJoinStats()
+        N.lib().gw_join_get_stats(self._h, ctypes.byref(s))
+        return s.as_dict()
+
+    @property
+    def stream(self) -> int:
+        return N.lib().gw_join_stream(self._h) or 0
+
+
+class JoinedStreams:
+    """stream.join(other) -- JoinedStreams (RS/api/datastream/JoinedStreams.java): where(k1)
+    .equal_to(k2).window(assigner).apply(join_function).execute_and_collect()."""
+
+    def __init__(self, left: "DataStream", right: "DataStream"):
+        self.left, self.right = left, right
+        self._k1 = self._k2 = None
+        self.assigner = None
+        self._fn = None
+
+    def where(self, key_selector) -> "JoinedStreams":
+        self._k1 = key_selector
+        return self
+
+    def equal_to(self, key_selector) -> "JoinedStreams":
+        if self._k1 is None:
+            raise ValueError("where() before equal_to()")
+        self._k2 = key_selector
+        return self
+
+    equalTo = equal_to
+
+    def window(self, assigner: WindowAssigner) -> "JoinedStreams":
+        if self._k2 is None:
+            raise ValueError("where().equal_to() before window()")
+        _join_geometry(assigner)  # session and count windows: unsupported
+        self.assigner = assigner
+        return self
+
+    def apply(self, join_function: Callable) -> "JoinedStreams":
+        if self.assigner is None:
+            raise ValueError("window() before apply()")
+        self._fn = join_function
+        return self
+
+    def execute_and_collect(self) -> list:
+        """Both bounded sources through one join operator, the left source first (the interleaving
+        of the sides does not matter to a window join); returns join_function(left, right) per
+        pair as StreamRecords with timestamp end - 1, in the operator's order.  Non-integer keys
+        get ids in their sorted order, so "keys ascending" is the keys' own order."""
+        if self._fn is None:
+            raise ValueError("apply() before execute_and_collect()")
+        lefts = [e for e in self.left.elements if isinstance(e, StreamRecord)]
+        rights = [e for e in self.right.elements if isinstance(e, StreamRecord)]
+        keys_in, keys_out = {}, []
+
+        def kid(key):
+            if key not in keys_in:
+                keys_in[key] = len(keys_out)
+                keys_out.append(key)
+            return keys_in[key]
+
+        # keys ordered as the operator orders them: ids follow the sorted distinct keys
+        allk = [self._k1(e.value) for e in lefts] + [self._k2(e.value) for e in rights]
+        int_keys = all(isinstance(k, int) and not isinstance(k, bool) and LONG_MIN <= k <= LONG_MAX for k in allk)
+        if not int_keys:
+            for k in sorted(set(allk), key=lambda k: (type(k).__name__, k)):
+                kid(k)
+        enc = (lambda k: k) if int_keys else kid
+        out = []
+        kw = {k: v for k, v in self.left.env.op_kwargs.items() if k in ("device", "capacity_hint", "max_batch")}
+        with GpuWindowJoinOperator(self.assigner, **kw) as op:
+            # the two-input operator's watermark is the minimum of its inputs' (AbstractStreamOperator
+            # .processWatermark1/2): with each bounded source fed whole, the first one is end of input
+            for side, elems, sel in ((op.LEFT, lefts, self._k1), (op.RIGHT, rights, self._k2)):
+                if elems:
+                    op.process_batch(side, [enc(sel(e.value)) for e in elems], [int(e.timestamp) for e in elems],
+                                     list(range(len(elems))))
+            op.end_input()
+            _, _, e, lp, rp = op.drain()
+            for i in range(len(e)):
+                out.append(StreamRecord(self._fn(lefts[int(lp[i])].value, rights[int(rp[i])].value), int(e[i]) - 1))
+        return out
+
+
 class WindowedStream:
     """keyBy(...).window(assigner) — WindowedStream (RS/api/datastream/WindowedStream.java:84-96)."""
 
@@ -1244,13 +1506,18 @@ class KeyedStream:
 
 
 class DataStream:
-    def __init__(self, env):
+    def __init__(self, env, elements=None):
         self.env = env
+        self.elements = env.elements if elements is None else elements  # this stream's own source
 
     def key_by(self, key_selector) -> KeyedStream:
         return KeyedStream(self.env, key_selector)
 
     keyBy = key_by
+
+    def join(self, other: "DataStream") -> JoinedStreams:
+        """DataStream.join (RS/api/datastream/DataStream.java): a window join with `other`."""
+        return JoinedStreams(self, other)
 
 
 class StreamExecutionEnvironment:
@@ -1267,7 +1534,7 @@ class StreamExecutionEnvironment:
 
     def from_elements(self, elements: Iterable) -> DataStream:
         self.elements = list(elements)
-        return DataStream(self)
+        return DataStream(self, self.elements)
 
 
 # Keyed snapshot: a gw_snapshot blob plus its key table (id -> key), what the Java operator

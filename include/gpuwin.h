@@ -520,6 +520,115 @@ int  gw_top_n_host(int64_t n, const int64_t* key, const int64_t* start, const in
                    int32_t top, int32_t mode, int64_t* key_out, int64_t* start_out, int64_t* end_out,
                    void* result_out, int64_t* win_rows_out, int64_t cap, int64_t* n_out);
 
+/* ---- event-time window join of two keyed streams ---------------------------------
+ * stream.join(other).where(k1).equalTo(k2).window(assigner).apply(JoinFunction): JoinedStreams /
+ * CoGroupedStreams (RS/api/datastream/JoinedStreams.java, CoGroupedStreams.java), Nexmark Q8.
+ * Flink tags and unions both inputs, keys the union and runs the same WindowOperator with
+ * ListState; at the fire JoinCoGroupFunction.coGroup emits the cross product of the two sides'
+ * elements per (key, window) (JoinedStreams.java, JoinCoGroupFunction).
+ *
+ * Records: side L (0) or R (1), (key, ts, payload) int64 columns; payload is the element as the
+ * caller packs or numbers it.  Assigners: tumbling (slide = size) and sliding, size > 0,
+ * slide > 0, |offset| < slide (GW_E_INVALID otherwise).  A record's windows are those of
+ * SlidingEventTimeWindows.assignWindows (:75-90): lastStart = TimeWindow.getWindowStartWithOffset
+ * (ts, offset, slide) (TimeWindow.java:264-272), starts lastStart - k * slide for k >= 0 while
+ * start > ts - size.  ts = Long.MIN_VALUE: GW_E_NO_TIMESTAMP; a window bound (or a step of the
+ * arithmetic) beyond int64: GW_E_RANGE; more than GW_JOIN_MAX_WINDOWS windows per record
+ * (ceil(size / slide)): GW_E_UNSUPPORTED.
+ * Firing: EventTimeTrigger, allowed lateness 0.  The watermark going from w0 to w1 > w0 fires the
+ * windows with w0 < end - 1 <= w1, each with the records ingested so far whose window set contains
+ * it.  A record ingested at watermark w is late when lastStart + size - 1 <= w (all its windows
+ * have passed): dropped and counted (numLateRecordsDropped, WindowOperator.java:440-446; with
+ * size < slide a record between two windows falls under the same test, where Flink tests its
+ * timestamp).  A record that is not late but has windows that passed never shows up in those.  A
+ * watermark that does not advance is ignored; end of input is Long.MAX_VALUE.
+ * Output of a fire: for every fired (window, key) with L >= 1 left and R >= 1 right records the
+ * L * R pairs (key, start, end, left payload, right payload); an inner join.  Order: windows by
+ * ascending end, within a window keys ascending (signed), within a (window, key) left-major, each
+ * side in arrival order (ingest call, then index): JoinCoGroupFunction.coGroup's nested loop.
+ * The emitted element's timestamp is end - 1, which gw_encode_rows_* writes: the five columns
+ * are the (key, start, end, 8 bytes, payload) columns it takes.
+ * Not offered: allowed lateness > 0, PurgingTrigger and evictors, session and count windows
+ * (GW_E_UNSUPPORTED at create), coGroup / outer joins, snapshots, key_hash columns, the RCCL
+ * exchange (partition the inputs with gw_partition_device), network-buffer ingest.
+ *
+ * gw_window_join_device: stateless; n_l left and n_r right records in arrival order in device
+ * columns, the geometry and the interval (w0, w1]; the pairs of the windows firing in it, in the
+ * order above, to five device columns of cap rows.  cap < the number of pairs: GW_E_OUTPUT_FULL,
+ * the needed number in *n_out, nothing written.  n_l = 0 or n_r = 0: GW_OK, no pairs.  At most
+ * 2^30 - 1 (record, fired window) tuples per call (GW_E_UNSUPPORTED); more than INT64_MAX / 40
+ * pairs: GW_E_RANGE.  Waits on `stream` (the host reads the tuple count and the pair count), using
+ * scratch of its own per device.  Errors: gw_last_error of NULL.
+ * gw_window_join_host: the same contract as plain host code over host arrays, no device: for a
+ * fire of a few records, or a process without a GPU.
+ * gw_window_join_device_timed: gw_window_join_device that also reports the time of its expand
+ * kernel between two HIP events (*expand_ms; 0 when no pair fired), for measurements.
+ *
+ * gw_join: the operator.  One append-only device log per side; gw_join_ingest* drops and counts
+ * the late records on the device and appends the rest (the log grows as needed).  gw_join_ingest_device
+ * orders itself with `stream` as gw_ingest_device does.  gw_join_advance_watermark fires
+ * (previous watermark, watermark] over the two logs, appends the pairs to the pending output
+ * (*pairs_fired, may be NULL: their number) and drops the records whose last window has fired.
+ * Pairs of several watermarks accumulate until drained or cleared: gw_join_drain copies up to cap
+ * and removes them (GW_E_OUTPUT_FULL while pairs remain), gw_join_rows_device is the zero-copy
+ * view, gw_join_clear_rows drops them.  After GW_E_NO_TIMESTAMP, GW_E_RANGE or a device error
+ * every call returns GW_E_STATE.  max_batch: records per device pass of an ingest (0: 2^22);
+ * capacity_hint: initial log rows per side. */
+#define GW_JOIN_MAX_WINDOWS 64
+#define GW_JOIN_LEFT  0
+#define GW_JOIN_RIGHT 1
+int  gw_window_join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                           int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                           int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+                           int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out, int64_t* d_lpay_out,
+                           int64_t* d_rpay_out, int64_t cap, int64_t* n_out, void* stream);
+int  gw_window_join_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                 int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                 int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+                                 int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out, int64_t* d_lpay_out,
+                                 int64_t* d_rpay_out, int64_t cap, int64_t* n_out, void* stream, double* expand_ms);
+int  gw_window_join_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                         const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
+                         int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out,
+                         int64_t* end_out, int64_t* lpay_out, int64_t* rpay_out, int64_t cap, int64_t* n_out);
+
+typedef struct gw_join gw_join;
+typedef struct gw_join_config {
+    int32_t assigner;        /* GW_TUMBLING or GW_SLIDING                         */
+    int64_t size;
+    int64_t slide;           /* GW_SLIDING only                                   */
+    int64_t offset;
+    int32_t device;
+    int64_t capacity_hint;   /* initial rows of each side's log (0: 16)           */
+    int64_t max_batch;       /* records per device pass of an ingest (0: 2^22)    */
+} gw_join_config;
+typedef struct gw_join_stats {
+    int64_t live_left, live_right;                  /* records in the logs        */
+    int64_t log_capacity_left, log_capacity_right;  /* rows allocated             */
+    int64_t fires;                                  /* watermarks that advanced   */
+    int64_t pairs_fired;
+    int64_t log_growths;
+    int64_t last_fire_tuples;                       /* (record, window) tuples    */
+} gw_join_stats;
+int  gw_join_create(const gw_join_config* cfg, gw_join** out);
+int  gw_join_destroy(gw_join* h);
+const char* gw_join_last_error(const gw_join* h);
+int  gw_join_ingest(gw_join* h, int32_t side, int64_t n, const int64_t* key, const int64_t* ts,
+                    const int64_t* payload);
+int  gw_join_ingest_device(gw_join* h, int32_t side, int64_t n, const int64_t* d_key, const int64_t* d_ts,
+                           const int64_t* d_payload, void* stream);
+int  gw_join_advance_watermark(gw_join* h, int64_t watermark, int64_t* pairs_fired);
+int  gw_join_end_input(gw_join* h, int64_t* pairs_fired);
+int  gw_join_pending(gw_join* h, int64_t* n);
+int  gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay,
+                   int64_t cap, int64_t* n);
+int  gw_join_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                         const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n);
+int  gw_join_clear_rows(gw_join* h);
+int64_t gw_join_late_dropped(const gw_join* h);
+int  gw_join_get_stats(const gw_join* h, gw_join_stats* out);
+void* gw_join_stream(gw_join* h);
+
 /* ---- network-buffer output: fired rows as serialized stream elements -------------
  * The output side's counterpart of gw_ingest_serialized*: instead of columns that the JVM turns
  * into one object per row and pushes through TimestampedCollector.collect and
