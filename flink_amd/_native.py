@@ -70,9 +70,16 @@ EXPORTS = [
     "gw_join_create", "gw_join_destroy", "gw_join_last_error", "gw_join_ingest", "gw_join_ingest_device",
     "gw_join_advance_watermark", "gw_join_end_input", "gw_join_pending", "gw_join_drain", "gw_join_rows_device",
     "gw_join_clear_rows", "gw_join_late_dropped", "gw_join_get_stats", "gw_join_stream",
+    "gw_window_join_outer_device", "gw_window_join_outer_device_timed", "gw_window_join_outer_host",
+    "gw_window_cogroup_device", "gw_window_cogroup_device_timed", "gw_window_cogroup_host",
+    "gw_join_set_mode", "gw_join_drain_outer", "gw_join_rows_device_outer", "gw_join_cogroup_pending",
+    "gw_join_cogroup_drain", "gw_join_cogroup_rows_device",
 ]
 JOIN_MAX_WINDOWS = 64  # gpuwin.h GW_JOIN_MAX_WINDOWS
 JOIN_LEFT, JOIN_RIGHT = 0, 1
+# gpuwin.h GW_JOIN_MODE_*: bit 0 keeps unmatched left records, bit 1 unmatched right records
+JOIN_MODE_INNER, JOIN_MODE_LEFT_OUTER, JOIN_MODE_RIGHT_OUTER, JOIN_MODE_FULL_OUTER, JOIN_MODE_COGROUP = 0, 1, 2, 3, 4
+JOIN_MODES = {"inner": 0, "left_outer": 1, "right_outer": 2, "full_outer": 3, "cogroup": 4}
 EXCHANGE_ID_BYTES = 128
 EXCHANGE_RECV_SETS = 3  # gpuwin.h GW_EXCHANGE_RECV_SETS
 
@@ -338,6 +345,25 @@ def lib() -> ctypes.CDLL:
         "gw_join_late_dropped": (i64, [p]),
         "gw_join_get_stats": (c_int, [p, ctypes.POINTER(GwJoinStats)]),
         "gw_join_stream": (p, [p]),
+        "gw_window_join_outer_device": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, i32, i64, p, p, p, p, p,
+                                                p, i64, P64, p]),
+        "gw_window_join_outer_device_timed": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, i32, i64, p, p, p,
+                                                      p, p, p, i64, P64, p, ctypes.POINTER(ctypes.c_double)]),
+        "gw_window_join_outer_host": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, i32, i64, p, p, p, p, p, p,
+                                              i64, P64]),
+        "gw_window_cogroup_device": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, p, p, p, p, p, p, i64, p,
+                                             i64, i64, P64, p]),
+        "gw_window_cogroup_device_timed": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, p, p, p, p, p, p, i64,
+                                                   p, i64, i64, P64, p, ctypes.POINTER(ctypes.c_double)]),
+        "gw_window_cogroup_host": (c_int, [i64, p, p, p, i64, p, p, p, i64, i64, i64, i64, i64, p, p, p, p, p, p, i64, p, i64,
+                                           i64, P64]),
+        "gw_join_set_mode": (c_int, [p, i32, i64]),
+        "gw_join_drain_outer": (c_int, [p, p, p, p, p, p, p, i64, P64]),
+        "gw_join_rows_device_outer": (c_int, [p, ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p),
+                                              ctypes.POINTER(p), ctypes.POINTER(p), P64]),
+        "gw_join_cogroup_pending": (c_int, [p, P64]),
+        "gw_join_cogroup_drain": (c_int, [p, p, p, p, p, p, p, i64, p, i64, i64, P64]),
+        "gw_join_cogroup_rows_device": (c_int, [p] + [ctypes.POINTER(p)] * 7 + [P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

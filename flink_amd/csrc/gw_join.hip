@@ -25,6 +25,17 @@
 //            16-byte store.  Work is split by output pairs, never by groups, so one group of
 //            4096 x 64 and a million groups of 1 x 1 are the same work per workgroup.
 //
+// stream.coGroup(other)... (CoGroupedStreams, the primitive under the join) shares count .. groups
+// and differs in what leaves (gw_window_join_outer_*, gw_window_cogroup_*, gw_join_set_mode):
+//
+//   outer    the left / right / full outer joins as modes of the expansion: a one-sided group
+//            the mode keeps becomes a descriptor of its own (L x 1 or 1 x R, the lacking side
+//            flagged), its rows carry the caller's null payload, and a `present` byte per row
+//            tells the kinds apart.  The expand kernel is instantiated per mode; the inner one
+//            knows nothing of this;
+//   cogroup  the group table itself as a CSR: two scans of the groups' L and R, one writer of
+//            the group rows, one pass that sends every sorted tuple's payload to its place.
+//
 // No atomics in the expand kernel; the scans are two-pass (block sums, one block over the sums,
 // a down-sweep); the only look-back is gw_sort.hip's own.  The host reads the device twice per
 // call: the tuple count (it sizes the sort) and the pair count (it sizes the output).
@@ -331,10 +342,15 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_group_fill(int64_t nt, co
         if ((gsrc[i] >> 31) && (h || !(gsrc[i - 1] >> 31))) gmid[g] = (uint32_t)i;
     }
 }
-// Over nt entries (the groups are the first hdr[JH_NG] of them): L * R and whether it is > 0.
+// A descriptor's R word: R below, and above it which side the group lacks (an outer join's
+// unmatched rows).  R < 2^30, so the inner join's words are plain R.
+constexpr uint32_t kDescNoLeft = 1u << 30, kDescNoRight = 1u << 31, kDescRMask = kDescNoLeft - 1;
+
+// Over nt entries (the groups are the first hdr[JH_NG] of them): the group's rows in `mode` (L * R,
+// or with one side empty L or R where the mode keeps that side) and whether it has any.
 __global__ void __launch_bounds__(kJoinThreads) k_join_group_prod(int64_t nt, const int64_t* __restrict__ hdr,
                                                                   const uint32_t* __restrict__ gfirst,
-                                                                  const uint32_t* __restrict__ gmid, int64_t* prod,
+                                                                  const uint32_t* __restrict__ gmid, int mode, int64_t* prod,
                                                                   uint32_t* ne) {
     const int64_t ng = hdr[JH_NG];
     for (int64_t g = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; g < nt; g += (int64_t)gridDim.x * kJoinThreads) {
@@ -342,14 +358,19 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_group_prod(int64_t nt, co
         if (g < ng) {
             const int64_t first = gfirst[g], end = g + 1 < ng ? (int64_t)gfirst[g + 1] : nt;
             const int64_t mid = gmid[g] == ~0u ? end : (int64_t)gmid[g];
-            p = (mid - first) * (end - mid);  // both below 2^30
+            const int64_t L = mid - first, R = end - mid;  // both below 2^30
+            p = L * R;
+            if (R == 0 && (mode & GW_JOIN_MODE_LEFT_OUTER)) p = L;
+            if (L == 0 && (mode & GW_JOIN_MODE_RIGHT_OUTER)) p = R;
         }
         prod[g] = p;
         ne[g] = p > 0;
     }
 }
-// Descriptors of the groups with pairs: pair offset, first left tuple, first right tuple, R, key
-// and window start; coff[nc] = the total.
+// Descriptors of the groups with rows: row offset, first left tuple, first right tuple, R, key
+// and window start; coff[nc] = the total.  A left-only group is L x 1 and a right-only group
+// 1 x R with the lacking side flagged in the R word; its tuple index is the group's first, so it
+// stays inside gpay whether or not a lane reads through it.
 __global__ void __launch_bounds__(kJoinThreads) k_join_compact(int64_t nt, const int64_t* __restrict__ hdr,
                                                                const uint32_t* __restrict__ gfirst,
                                                                const uint32_t* __restrict__ gmid,
@@ -368,8 +389,13 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_compact(int64_t nt, const
         const int64_t first = gfirst[g], end = g + 1 < ng ? (int64_t)gfirst[g + 1] : nt;
         coff[c] = poff[g];
         cfirst[c] = (uint32_t)first;
-        crb[c] = gmid[g];
-        cR[c] = (uint32_t)(end - (int64_t)gmid[g]);
+        if (gmid[g] == ~0u) {  // left only: kept by the mode, or prod[g] were 0
+            crb[c] = (uint32_t)first;
+            cR[c] = 1u | kDescNoRight;
+        } else {
+            crb[c] = gmid[g];
+            cR[c] = (uint32_t)(end - (int64_t)gmid[g]) | ((int64_t)gmid[g] == first ? kDescNoLeft : 0u);
+        }
         ckey[c] = gkey[first];
         cws[c] = (int64_t)((uint64_t)min_start + gord[first] * (uint64_t)slide);
     }
@@ -381,7 +407,9 @@ struct alignas(16) I64x2 {
     int64_t a, b;
 };
 struct JoinOut {
-    int64_t* col[5];  // key, start, end, left payload, right payload
+    int64_t* col[5];      // key, start, end, left payload, right payload
+    uint8_t* present;     // outer modes: 1 left only, 2 right only, 3 both (may be null)
+    int64_t null_payload; // outer modes: the lacking side's payload
 };
 
 // One wave: the largest c in [0, nc) with coff[c] <= p (coff[0] = 0 <= p), 64 probes a round.
@@ -403,9 +431,14 @@ struct Pair {
     int64_t key, ws, lp, rp;
 };
 
-// Output slot q holds pair q - shift: with shift = 1 the columns start 8 bytes past a 16-byte
-// boundary and pair 0 is written alone, so every two-pair store is aligned.
-template <bool VEC>
+// Output slot q holds row q - shift: with shift = 1 the columns start 8 bytes past a 16-byte
+// boundary and row 0 is written alone, so every two-row store is aligned.
+// MODE: the GW_JOIN_MODE_* of the call.  The inner join (0) knows no flagged descriptor and is
+// the kernel it was; an outer mode tests only the flags its descriptors can carry.  A lacking
+// side's tuples are never read: its payload is o.null_payload.  `present` takes the two rows of
+// a lane as one 2-byte store where that is aligned (always so for the operator, whose columns
+// and present bytes advance together) and as two bytes elsewhere.
+template <bool VEC, int MODE>
 __global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shift, int64_t nc,
                                                               const int64_t* __restrict__ coff,
                                                               const uint32_t* __restrict__ cfirst,
@@ -414,6 +447,8 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shi
                                                               const int64_t* __restrict__ ckey,
                                                               const int64_t* __restrict__ cws,
                                                               const int64_t* __restrict__ gpay, int64_t size, JoinOut o) {
+    constexpr bool kNoRight = (MODE & GW_JOIN_MODE_LEFT_OUTER) != 0;  // left-only descriptors occur
+    constexpr bool kNoLeft = (MODE & GW_JOIN_MODE_RIGHT_OUTER) != 0;  // right-only descriptors occur
     __shared__ int64_t s_off[kExpTile + 1];
     __shared__ uint32_t s_first[kExpTile], s_rb[kExpTile], s_R[kExpTile];
     __shared__ int64_t s_c[2];
@@ -427,7 +462,7 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shi
     }
     __syncthreads();
     const int64_t c0 = s_c[0];
-    const int ngt = (int)(s_c[1] - c0) + 1;  // <= kExpTile: every descriptor has a pair in the tile
+    const int ngt = (int)(s_c[1] - c0) + 1;  // <= kExpTile: every descriptor has a row in the tile
     for (int i = threadIdx.x; i <= ngt; i += kJoinThreads) {
         s_off[i] = coff[c0 + i];
         if (i < ngt) {
@@ -451,6 +486,11 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shi
         }
         const uint64_t r = (uint64_t)(p - s_off[lo]);
         uint32_t R = s_R[lo];
+        uint32_t fx = 0;  // the sides x's descriptor lacks: 1 left, 2 right
+        if constexpr (MODE != 0) {
+            fx = R >> 30;
+            R &= kDescRMask;  // >= 1: a left-only descriptor is L x 1
+        }
         uint64_t li, rj;
         if (r >> 32) {
             li = r / R;
@@ -459,24 +499,27 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shi
             li = (uint32_t)r / R;
             rj = (uint32_t)r - (uint32_t)li * R;
         }
+        const bool xl = !(kNoLeft && (fx & 1)), xr = !(kNoRight && (fx & 2));
         Pair x, y;
         x.key = ckey[c0 + lo];
         x.ws = cws[c0 + lo];
-        x.lp = gpay[s_first[lo] + li];
-        x.rp = gpay[s_rb[lo] + rj];
+        x.lp = xl ? gpay[s_first[lo] + li] : o.null_payload;
+        x.rp = xr ? gpay[s_rb[lo] + rj] : o.null_payload;
         y = x;
+        uint32_t fy = fx;
         if (va && vb) {
-            if (pb >= s_off[lo + 1]) {  // the next descriptor: its pair 0
+            if (pb >= s_off[lo + 1]) {  // the next descriptor: its row 0
                 ++lo;
+                if constexpr (MODE != 0) fy = s_R[lo] >> 30;
                 y.key = ckey[c0 + lo];
                 y.ws = cws[c0 + lo];
-                y.lp = gpay[s_first[lo]];
-                y.rp = gpay[s_rb[lo]];
-            } else if (rj + 1 < R) {
+                y.lp = !(kNoLeft && (fy & 1)) ? gpay[s_first[lo]] : o.null_payload;
+                y.rp = !(kNoRight && (fy & 2)) ? gpay[s_rb[lo]] : o.null_payload;
+            } else if (rj + 1 < R) {  // (R > 1: the descriptor has right tuples)
                 y.rp = gpay[s_rb[lo] + rj + 1];
-            } else {
+            } else {  // (li + 1 < L: the descriptor has left tuples)
                 y.lp = gpay[s_first[lo] + li + 1];
-                y.rp = gpay[s_rb[lo]];
+                if (xr) y.rp = gpay[s_rb[lo]];
             }
         }
         if (VEC && va && vb) {
@@ -493,6 +536,17 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_expand(int64_t P, int shi
             if (vb) {
                 o.col[0][pb] = y.key; o.col[1][pb] = y.ws; o.col[2][pb] = y.ws + size;
                 o.col[3][pb] = y.lp; o.col[4][pb] = y.rp;
+            }
+        }
+        if constexpr (MODE != 0) {
+            if (o.present) {
+                const uint32_t bx = 3u ^ fx, by = 3u ^ fy;
+                if (va && vb && !((uintptr_t)(o.present + pa) & 1)) {
+                    *reinterpret_cast<uint16_t*>(o.present + pa) = (uint16_t)(bx | by << 8);
+                } else {
+                    if (va) o.present[pa] = (uint8_t)bx;
+                    if (vb) o.present[pb] = (uint8_t)by;
+                }
             }
         }
     }
@@ -551,49 +605,127 @@ struct TupArrays {  // by tuples
         ord0 = c.take<uint64_t>(nt); ord1 = c.take<uint64_t>(nt); gord = c.take<uint64_t>(nt);
         v0 = c.take<uint32_t>(nt); v1 = c.take<uint32_t>(nt); src = c.take<uint32_t>(nt); gsrc = c.take<uint32_t>(nt);
         head = c.take<uint32_t>(nt); hex = c.take<uint32_t>(nt); gfirst = c.take<uint32_t>(nt);
-        gmid = c.take<uint32_t>(nt); ne = c.take<uint32_t>(nt); cidx = c.take<uint32_t>(nt);
+        // (nt + 1: a coGroup keeps its per-group L and R in ne and cidx and their scans, with the
+        // totals as entry ng, in poff and coff)
+        gmid = c.take<uint32_t>(nt); ne = c.take<uint32_t>(nt + 1); cidx = c.take<uint32_t>(nt + 1);
         cfirst = c.take<uint32_t>(nt); crb = c.take<uint32_t>(nt); cR = c.take<uint32_t>(nt);
-        gkey = c.take<int64_t>(nt); gpay = c.take<int64_t>(nt); prod = c.take<int64_t>(nt); poff = c.take<int64_t>(nt);
+        gkey = c.take<int64_t>(nt); gpay = c.take<int64_t>(nt); prod = c.take<int64_t>(nt); poff = c.take<int64_t>(nt + 1);
         coff = c.take<int64_t>(nt + 1); ckey = c.take<int64_t>(nt); cws = c.take<int64_t>(nt);
-        blk = c.take<int64_t>(scan_blocks(nt) + 1);
+        blk = c.take<int64_t>(scan_blocks(nt + 1) + 1);
         sort = c.take<char>(sort_scratch_bytes(nt));
     }
 };
 
-// provide(total, out): the caller's output columns for `total` pairs (or an error).
-typedef std::function<int(int64_t, JoinOut&, std::string&)> JoinProvide;
+// ---- coGroup: the group table itself, as a CSR over two element columns ----------------------
+// Over nt + 1 entries: the group's L and R, 0 past the groups, so that entry ng of their
+// exclusive scans is the total.
+__global__ void __launch_bounds__(kJoinThreads) k_cogroup_sizes(int64_t nt, const int64_t* __restrict__ hdr,
+                                                                const uint32_t* __restrict__ gfirst,
+                                                                const uint32_t* __restrict__ gmid, uint32_t* gl,
+                                                                uint32_t* gr) {
+    const int64_t ng = hdr[JH_NG];
+    for (int64_t g = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; g <= nt; g += (int64_t)gridDim.x * kJoinThreads) {
+        uint32_t L = 0, R = 0;
+        if (g < ng) {
+            const int64_t first = gfirst[g], end = g + 1 < ng ? (int64_t)gfirst[g + 1] : nt;
+            const int64_t mid = gmid[g] == ~0u ? end : (int64_t)gmid[g];
+            L = (uint32_t)(mid - first);
+            R = (uint32_t)(end - mid);
+        }
+        gl[g] = L;
+        gr[g] = R;
+    }
+}
+struct CoGroupOut {
+    int64_t *key, *start, *end, *loff, *roff;  // rows of this fire's groups (loff, roff: one more)
+    int64_t *lelem, *relem;                    // the element columns from their row 0
+    int64_t lbase, rbase;                      // elements ahead of this fire's: the offsets' base
+};
+// Group g's key, window and offsets; entry ng closes the offsets with the totals.
+__global__ void __launch_bounds__(kJoinThreads) k_cogroup_groups(const int64_t* __restrict__ hdr,
+                                                                 const uint32_t* __restrict__ gfirst,
+                                                                 const int64_t* __restrict__ gkey,
+                                                                 const uint64_t* __restrict__ gord, int64_t min_start,
+                                                                 int64_t slide, int64_t size,
+                                                                 const int64_t* __restrict__ loff,
+                                                                 const int64_t* __restrict__ roff, CoGroupOut o) {
+    const int64_t ng = hdr[JH_NG];
+    for (int64_t g = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; g <= ng; g += (int64_t)gridDim.x * kJoinThreads) {
+        o.loff[g] = o.lbase + loff[g];
+        o.roff[g] = o.rbase + roff[g];
+        if (g == ng) continue;
+        const uint32_t first = gfirst[g];
+        const int64_t ws = (int64_t)((uint64_t)min_start + gord[first] * (uint64_t)slide);
+        o.key[g] = gkey[first];
+        o.start[g] = ws;
+        o.end[g] = ws + size;
+    }
+}
+// Sorted tuple i of group g goes to its side's column at the group's offset plus its rank in
+// the group's side (the sort kept each side in arrival order).
+__global__ void __launch_bounds__(kJoinThreads) k_cogroup_elems(int64_t nt, const uint32_t* __restrict__ head,
+                                                                const uint32_t* __restrict__ hex,
+                                                                const uint32_t* __restrict__ gsrc,
+                                                                const uint32_t* __restrict__ gfirst,
+                                                                const uint32_t* __restrict__ gmid,
+                                                                const int64_t* __restrict__ gpay,
+                                                                const int64_t* __restrict__ loff,
+                                                                const int64_t* __restrict__ roff, CoGroupOut o) {
+    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < nt; i += (int64_t)gridDim.x * kJoinThreads) {
+        const uint32_t g = hex[i] + head[i] - 1;
+        if (gsrc[i] >> 31)
+            o.relem[o.rbase + roff[g] + (i - (int64_t)gmid[g])] = gpay[i];
+        else
+            o.lelem[o.lbase + loff[g] + (i - (int64_t)gfirst[g])] = gpay[i];
+    }
+}
 
-struct JoinTimes {  // HIP events around the expand kernel (scripts/join_bench.py)
+// provide(total, out): the caller's output columns for `total` rows (or an error).
+typedef std::function<int(int64_t, JoinOut&, std::string&)> JoinProvide;
+// provide(groups, left elements, right elements, out): the caller's CSR columns (or an error).
+typedef std::function<int(int64_t, int64_t, int64_t, CoGroupOut&, std::string&)> CoGroupProvide;
+
+struct JoinTimes {  // HIP events around the expand kernel or the coGroup writers (scripts/join_bench.py)
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
-int join_run(const JoinIn& a, const JoinProvide& provide, int64_t* n_pairs, int64_t* n_tuples, hipStream_t s,
-             std::string& why, const JoinTimes* times = nullptr) {
-    static std::mutex mu;
-    static Scratch scr_rec[64], scr_tup[64];
-    *n_pairs = 0;
+// One call at a time per process: every call waits for its launches before it returns, so the
+// per-device scratch is free for the next.
+static std::mutex g_join_mu;
+static Scratch g_scr_rec[64], g_scr_tup[64];
+
+struct JoinStage {  // what stages count .. groups leave behind (g_join_mu held)
+    RecArrays R;
+    TupArrays T;
+    int64_t nt = 0, min_start = 0;
+    int64_t h[kJoinHdr];
+};
+static int join_dev_fail(hipError_t e, std::string& why) {
+    why = std::string("window join: ") + hipGetErrorString(e);
+    return GW_E_DEVICE;
+}
+
+// Stages count, emit, sort and groups: the sorted tuples (gkey, gord, gsrc, gpay) and the group
+// table (head, hex, gfirst, gmid; hdr[JH_NG] groups, on the device).  st.nt = 0: nothing fired.
+static int join_groups(const JoinIn& a, JoinStage& st, int64_t* n_tuples, hipStream_t s, std::string& why) {
     if (n_tuples) *n_tuples = 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { why = "window join: no device"; return GW_E_DEVICE; }
-    std::lock_guard<std::mutex> lock(mu);  // every call waits for its launches before it returns
-    auto dev_fail = [&](hipError_t e) {
-        why = std::string("window join: ") + hipGetErrorString(e);
-        return GW_E_DEVICE;
-    };
+    RecArrays& R = st.R;
+    TupArrays& T = st.T;
+    int64_t* h = st.h;
     Carve size_r{nullptr};
-    RecArrays R;
     R.carve(size_r, a.n);
-    int rc = scratch_ensure(scr_rec[dev], size_r.at, why);
+    int rc = scratch_ensure(g_scr_rec[dev], size_r.at, why);
     if (rc) return rc;
-    Carve cr{scr_rec[dev].p};
+    Carve cr{g_scr_rec[dev].p};
     R.carve(cr, a.n);
     hipLaunchKernelGGL(k_join_hdr_init, dim3(1), dim3(kJoinThreads), 0, s, R.hdr);
     hipLaunchKernelGGL(k_join_count, dim3(grid_for(a.n)), dim3(kJoinThreads), 0, s, a, R.cnt, R.hdr);
     hipError_t e = scan_excl<uint32_t, uint32_t>(R.cnt, R.toff, a.n, R.blk, R.hdr + JH_NT, s);
-    int64_t h[kJoinHdr];
-    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof st.h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return dev_fail(e);
+    if (e != hipSuccess) return join_dev_fail(e, why);
     if (h[JH_FLAGS] & GW_DF_NO_TS) {
         why = "Record has Long.MIN_VALUE timestamp (= no timestamp marker)";
         return GW_E_NO_TIMESTAMP;
@@ -605,58 +737,91 @@ int join_run(const JoinIn& a, const JoinProvide& provide, int64_t* n_pairs, int6
         why = "window join: more than 2^30 - 1 (record, fired window) tuples in one fire";
         return GW_E_UNSUPPORTED;
     }
-    if (nt == 0) {
-        JoinOut none{};
-        return provide(0, none, why);
-    }
-    const int64_t min_start = h[JH_MINS];
+    st.nt = nt;
+    if (nt == 0) return GW_OK;
+    const int64_t min_start = st.min_start = h[JH_MINS];
     const uint64_t min_kw = (uint64_t)h[JH_MINK];
     const int kbits = bit_length((uint64_t)h[JH_MAXK] - min_kw);
     const int obits = bit_length(((uint64_t)h[JH_MAXS] - (uint64_t)min_start) / (uint64_t)a.g.slide);
     Carve size_t_{nullptr};
-    TupArrays T;
     T.carve(size_t_, nt);
-    if ((rc = scratch_ensure(scr_tup[dev], size_t_.at, why))) return rc;
-    Carve ct{scr_tup[dev].p};
+    if ((rc = scratch_ensure(g_scr_tup[dev], size_t_.at, why))) return rc;
+    Carve ct{g_scr_tup[dev].p};
     T.carve(ct, nt);
     const int gt = grid_for(nt);
     hipLaunchKernelGGL(k_join_emit, dim3(grid_for(a.n)), dim3(kJoinThreads), 0, s, a, R.toff, min_start, min_kw, T.kw0, T.ord,
                        T.src);
-    if ((e = hipGetLastError()) != hipSuccess) return dev_fail(e);
+    if ((e = hipGetLastError()) != hipSuccess) return join_dev_fail(e, why);
     // by key word, then by window ordinal: both stable, so a group keeps left before right and
     // each side its arrival order
     int alt = 0;
-    if ((e = sort_pairs_u64(T.kw0, T.v0, T.kw1, T.v1, nt, 0, kbits, T.sort, s, &alt, true)) != hipSuccess) return dev_fail(e);
+    if ((e = sort_pairs_u64(T.kw0, T.v0, T.kw1, T.v1, nt, 0, kbits, T.sort, s, &alt, true)) != hipSuccess)
+        return join_dev_fail(e, why);
     uint32_t* perm = alt ? T.v1 : T.v0;
     if (obits > 0) {
         uint32_t* other = alt ? T.v0 : T.v1;
         hipLaunchKernelGGL(k_join_gather_ord, dim3(gt), dim3(kJoinThreads), 0, s, nt, perm, T.ord, T.ord0);
         if ((e = sort_pairs_u64(T.ord0, perm, T.ord1, other, nt, 0, obits, T.sort, s, &alt, false)) != hipSuccess)
-            return dev_fail(e);
+            return join_dev_fail(e, why);
         if (alt) perm = other;
     }
     hipLaunchKernelGGL(k_join_gather, dim3(gt), dim3(kJoinThreads), 0, s, a, nt, perm, T.ord, T.src, T.gkey, T.gord, T.gsrc,
                        T.gpay);
     hipLaunchKernelGGL(k_join_heads, dim3(gt), dim3(kJoinThreads), 0, s, nt, T.gkey, T.gord, T.head);
-    if ((e = scan_excl<uint32_t, uint32_t>(T.head, T.hex, nt, T.blk, R.hdr + JH_NG, s)) != hipSuccess) return dev_fail(e);
-    if ((e = hipMemsetAsync(T.gmid, 0xFF, (size_t)nt * 4, s)) != hipSuccess) return dev_fail(e);
+    if ((e = scan_excl<uint32_t, uint32_t>(T.head, T.hex, nt, T.blk, R.hdr + JH_NG, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = hipMemsetAsync(T.gmid, 0xFF, (size_t)nt * 4, s)) != hipSuccess) return join_dev_fail(e, why);
     hipLaunchKernelGGL(k_join_group_fill, dim3(gt), dim3(kJoinThreads), 0, s, nt, T.head, T.hex, T.gsrc, T.gfirst, T.gmid);
-    hipLaunchKernelGGL(k_join_group_prod, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, T.prod, T.ne);
-    if ((e = scan_excl<int64_t, int64_t>(T.prod, T.poff, nt, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return dev_fail(e);
-    if ((e = scan_excl<uint32_t, uint32_t>(T.ne, T.cidx, nt, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return dev_fail(e);
+    if ((e = hipGetLastError()) != hipSuccess) return join_dev_fail(e, why);
+    return GW_OK;
+}
+
+template <int MODE>
+static void launch_expand(bool vec, int64_t nblk, hipStream_t s, int64_t total, int shift, int64_t nc, const TupArrays& T,
+                          int64_t size, const JoinOut& out) {
+    if (vec)
+        hipLaunchKernelGGL((k_join_expand<true, MODE>), dim3((unsigned)nblk), dim3(kJoinThreads), 0, s, total, shift, nc,
+                           T.coff, T.cfirst, T.crb, T.cR, T.ckey, T.cws, T.gpay, size, out);
+    else
+        hipLaunchKernelGGL((k_join_expand<false, MODE>), dim3((unsigned)nblk), dim3(kJoinThreads), 0, s, total, shift, nc,
+                           T.coff, T.cfirst, T.crb, T.cR, T.ckey, T.cws, T.gpay, size, out);
+}
+
+// mode: GW_JOIN_MODE_INNER .. FULL_OUTER; the rows carry null_payload for a lacking side, and
+// out.present (when provide leaves one) says which sides a row has.  max_rows: the byte bound.
+int join_run(const JoinIn& a, int mode, int64_t null_payload, int64_t max_rows, const JoinProvide& provide,
+             int64_t* n_pairs, int64_t* n_tuples, hipStream_t s, std::string& why, const JoinTimes* times = nullptr) {
+    *n_pairs = 0;
+    std::lock_guard<std::mutex> lock(g_join_mu);
+    JoinStage st;
+    int rc = join_groups(a, st, n_tuples, s, why);
+    if (rc) return rc;
+    const int64_t nt = st.nt;
+    if (nt == 0) {
+        JoinOut none{};
+        return provide(0, none, why);
+    }
+    RecArrays& R = st.R;
+    TupArrays& T = st.T;
+    int64_t* h = st.h;
+    const int gt = grid_for(nt);
+    hipError_t e;
+    hipLaunchKernelGGL(k_join_group_prod, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, mode, T.prod, T.ne);
+    if ((e = scan_excl<int64_t, int64_t>(T.prod, T.poff, nt, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = scan_excl<uint32_t, uint32_t>(T.ne, T.cidx, nt, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return join_dev_fail(e, why);
     hipLaunchKernelGGL(k_join_compact, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, T.prod, T.poff, T.cidx,
-                       T.gkey, T.gord, min_start, a.g.slide, T.coff, T.cfirst, T.crb, T.cR, T.ckey, T.cws);
+                       T.gkey, T.gord, st.min_start, a.g.slide, T.coff, T.cfirst, T.crb, T.cR, T.ckey, T.cws);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof st.h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return dev_fail(e);
+    if (e != hipSuccess) return join_dev_fail(e, why);
     const int64_t total = h[JH_TOTAL], nc = h[JH_NC];
-    if (total > INT64_MAX / 40) { why = "window join: the pairs of one fire exceed int64 bytes"; return GW_E_RANGE; }
+    if (total > max_rows) { why = "window join: the pairs of one fire exceed int64 bytes"; return GW_E_RANGE; }
     *n_pairs = total;
     JoinOut out{};
     if ((rc = provide(total, out, why))) return rc;
     if (total == 0) return GW_OK;
-    // two pairs per 16-byte store need the five columns at one alignment
+    out.null_payload = null_payload;
+    // two rows per 16-byte store need the five columns at one alignment
     int par[5];
     for (int c = 0; c < 5; ++c) par[c] = (int)(((uintptr_t)out.col[c] >> 3) & 1);
     const bool vec = par[0] == par[1] && par[0] == par[2] && par[0] == par[3] && par[0] == par[4] &&
@@ -664,16 +829,58 @@ int join_run(const JoinIn& a, const JoinProvide& provide, int64_t* n_pairs, int6
     const int shift = vec ? par[0] : 0;
     const int64_t nblk = (total + shift + kExpTile - 1) / kExpTile;
     if (times) (void)hipEventRecord(times->e0, s);
-    if (vec)
-        hipLaunchKernelGGL(k_join_expand<true>, dim3((unsigned)nblk), dim3(kJoinThreads), 0, s, total, shift, nc, T.coff,
-                           T.cfirst, T.crb, T.cR, T.ckey, T.cws, T.gpay, a.g.size, out);
-    else
-        hipLaunchKernelGGL(k_join_expand<false>, dim3((unsigned)nblk), dim3(kJoinThreads), 0, s, total, shift, nc, T.coff,
-                           T.cfirst, T.crb, T.cR, T.ckey, T.cws, T.gpay, a.g.size, out);
+    switch (mode) {
+        case GW_JOIN_MODE_INNER:  // every row has both sides
+            if (out.present && (e = hipMemsetAsync(out.present, 3, (size_t)total, s)) != hipSuccess) return join_dev_fail(e, why);
+            launch_expand<GW_JOIN_MODE_INNER>(vec, nblk, s, total, shift, nc, T, a.g.size, out);
+            break;
+        case GW_JOIN_MODE_LEFT_OUTER: launch_expand<GW_JOIN_MODE_LEFT_OUTER>(vec, nblk, s, total, shift, nc, T, a.g.size, out); break;
+        case GW_JOIN_MODE_RIGHT_OUTER: launch_expand<GW_JOIN_MODE_RIGHT_OUTER>(vec, nblk, s, total, shift, nc, T, a.g.size, out); break;
+        default: launch_expand<GW_JOIN_MODE_FULL_OUTER>(vec, nblk, s, total, shift, nc, T, a.g.size, out); break;
+    }
     e = hipGetLastError();
     if (times) (void)hipEventRecord(times->e1, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // the scratch is free for the next call
-    if (e != hipSuccess) return dev_fail(e);
+    if (e != hipSuccess) return join_dev_fail(e, why);
+    return GW_OK;
+}
+
+// The fired groups as a CSR: n[0] groups, n[1] left and n[2] right elements.
+int cogroup_run(const JoinIn& a, const CoGroupProvide& provide, int64_t* n, int64_t* n_tuples, hipStream_t s,
+                std::string& why, const JoinTimes* times = nullptr) {
+    n[0] = n[1] = n[2] = 0;
+    std::lock_guard<std::mutex> lock(g_join_mu);
+    JoinStage st;
+    int rc = join_groups(a, st, n_tuples, s, why);
+    if (rc) return rc;
+    const int64_t nt = st.nt;
+    CoGroupOut out{};
+    if (nt == 0) return provide(0, 0, 0, out, why);
+    RecArrays& R = st.R;
+    TupArrays& T = st.T;
+    int64_t* h = st.h;
+    uint32_t *gl = T.ne, *gr = T.cidx;  // per group L and R, nt + 1 entries
+    int64_t *loff = T.poff, *roff = T.coff;
+    hipError_t e;
+    hipLaunchKernelGGL(k_cogroup_sizes, dim3(grid_for(nt + 1)), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, gl, gr);
+    if ((e = scan_excl<uint32_t, int64_t>(gl, loff, nt + 1, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = scan_excl<uint32_t, int64_t>(gr, roff, nt + 1, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = hipMemcpyAsync(h, R.hdr, sizeof st.h, hipMemcpyDeviceToHost, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return join_dev_fail(e, why);
+    const int64_t ng = h[JH_NG];
+    n[0] = ng;
+    n[1] = h[JH_TOTAL];
+    n[2] = h[JH_NC];
+    if ((rc = provide(n[0], n[1], n[2], out, why))) return rc;
+    if (times) (void)hipEventRecord(times->e0, s);
+    hipLaunchKernelGGL(k_cogroup_groups, dim3(grid_for(ng + 1)), dim3(kJoinThreads), 0, s, R.hdr, T.gfirst, T.gkey, T.gord,
+                       st.min_start, a.g.slide, a.g.size, loff, roff, out);
+    hipLaunchKernelGGL(k_cogroup_elems, dim3(grid_for(nt)), dim3(kJoinThreads), 0, s, nt, T.head, T.hex, T.gsrc, T.gfirst,
+                       T.gmid, T.gpay, loff, roff, out);
+    e = hipGetLastError();
+    if (times) (void)hipEventRecord(times->e1, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the scratch is free for the next call
+    if (e != hipSuccess) return join_dev_fail(e, why);
     return GW_OK;
 }
 
@@ -737,7 +944,17 @@ struct gw_join {
     DevCols<3> log[2], alt, stage;
     int64_t n_log[2] = {0, 0};
     DevCols<5> out;
+    DevBuf<uint8_t> pres;  // the rows' `present` bytes, row for row with `out`
     int64_t out_from = 0, pending = 0;
+    // gw_join_set_mode; `touched` once an ingest or a watermark has come
+    int32_t mode = GW_JOIN_MODE_INNER;
+    int64_t null_payload = 0;
+    bool touched = false;
+    // coGroup mode: pending groups (key, start, end, loff, roff; the offsets one row more) and
+    // the two element columns, all from row 0
+    DevCols<5> cg;
+    DevCols<1> cg_elem[2];
+    int64_t cg_n[3] = {0, 0, 0};  // groups, left elements, right elements
     DevBuf<char> scr;
     int64_t wm = INT64_MIN, late = 0, max_batch = 0;
     bool failed = false;
@@ -816,18 +1033,39 @@ struct gw_join {
     int reserve_out(int64_t more) {
         if (out_from + pending + more <= out.cap) return GW_OK;
         const int64_t cap = std::max<int64_t>(pending + more, 2 * out.cap);
-        if (out.reserve_keep(cap, out_from, pending, stream) != hipSuccess) {
+        if (out.reserve_keep(cap, out_from, pending, stream) != hipSuccess ||
+            pres.reserve_keep(cap, out_from, pending, stream) != hipSuccess) {
             (void)hipGetLastError();
             return fail(GW_E_OOM, "window join: out of device memory for %lld pending pairs", (long long)(pending + more));
         }
         out_from = 0;
         return GW_OK;
     }
+    // room for `more` groups and elements behind the pending CSR (the offsets: one row more)
+    int reserve_cogroup(const int64_t more[3]) {
+        hipError_t e = hipSuccess;
+        const int64_t need_g = cg_n[0] + more[0] + 1;
+        if (need_g > cg.cap) e = cg.reserve_keep(std::max<int64_t>(need_g, 2 * cg.cap), 0, cg.cap ? cg_n[0] + 1 : 0, stream);
+        for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
+            const int64_t need = cg_n[1 + sd] + more[1 + sd];
+            if (need > cg_elem[sd].cap)
+                e = cg_elem[sd].reserve_keep(std::max<int64_t>(need, 2 * cg_elem[sd].cap), 0, cg_n[1 + sd], stream);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(GW_E_OOM, "window join: out of device memory for %lld pending groups", (long long)(cg_n[0] + more[0]));
+        }
+        return GW_OK;
+    }
     int advance(int64_t w, int64_t* pairs_fired) {
         if (pairs_fired) *pairs_fired = 0;
+        touched = true;
         if (w <= wm) return GW_OK;  // a watermark that does not advance is ignored
         int64_t fired = 0, tuples = 0;
-        if (n_log[0] > 0 && n_log[1] > 0) {
+        // a side without records still fires where the mode keeps the other side's
+        const bool keep_l = mode == GW_JOIN_MODE_COGROUP || (mode & GW_JOIN_MODE_LEFT_OUTER);
+        const bool keep_r = mode == GW_JOIN_MODE_COGROUP || (mode & GW_JOIN_MODE_RIGHT_OUTER);
+        if ((n_log[0] > 0 || keep_r) && (n_log[1] > 0 || keep_l) && n_log[0] + n_log[1] > 0) {
             JoinIn a{};
             for (int sd = 0; sd < 2; ++sd) {
                 a.key[sd] = log[sd][0];
@@ -840,14 +1078,32 @@ struct gw_join {
             a.w0 = wm;
             a.w1 = w;
             std::string why;
-            const int rc = join_run(a, [&](int64_t total, JoinOut& o, std::string&) {
-                int r = reserve_out(total);
-                if (r) return r;
-                for (int c = 0; c < 5; ++c) o.col[c] = out[c] + out_from + pending;
-                return (int)GW_OK;
-            }, &fired, &tuples, stream, why);
-            if (rc) return failed ? rc : fail(rc, "%s", why.c_str());
-            pending += fired;
+            int rc;
+            if (mode == GW_JOIN_MODE_COGROUP) {
+                int64_t n3[3];
+                rc = cogroup_run(a, [&](int64_t ng, int64_t nl, int64_t nr, CoGroupOut& o, std::string&) {
+                    if (ng == 0) return (int)GW_OK;
+                    const int64_t more[3] = {ng, nl, nr};
+                    int r = reserve_cogroup(more);
+                    if (r) return r;
+                    o = CoGroupOut{cg[0] + cg_n[0], cg[1] + cg_n[0], cg[2] + cg_n[0], cg[3] + cg_n[0], cg[4] + cg_n[0],
+                                   cg_elem[0][0], cg_elem[1][0], cg_n[1], cg_n[2]};
+                    return (int)GW_OK;
+                }, n3, &tuples, stream, why);
+                if (rc) return failed ? rc : fail(rc, "%s", why.c_str());
+                fired = n3[0];
+                for (int c = 0; c < 3; ++c) cg_n[c] += n3[c];
+            } else {
+                rc = join_run(a, mode, null_payload, INT64_MAX / (mode ? 41 : 40), [&](int64_t total, JoinOut& o, std::string&) {
+                    int r = reserve_out(total);
+                    if (r) return r;
+                    for (int c = 0; c < 5; ++c) o.col[c] = out[c] + out_from + pending;
+                    o.present = pres.p + out_from + pending;
+                    return (int)GW_OK;
+                }, &fired, &tuples, stream, why);
+                if (rc) return failed ? rc : fail(rc, "%s", why.c_str());
+                pending += fired;
+            }
         }
         // the records whose last window has fired leave the logs
         for (int sd = 0; sd < 2; ++sd) {
@@ -897,20 +1153,29 @@ int join_args(int64_t n_l, int64_t n_r, int64_t size, int64_t slide, int64_t off
 
 extern "C" {
 
-// gw_window_join_device, with the expand kernel's time in *expand_ms when that is not null.
+// gw_window_join_device / _outer_device, with the expand kernel's time in *expand_ms when that
+// is not null.  max_rows: INT64_MAX / bytes per row.
 static int join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay, int64_t n_r,
                        const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay, int64_t size, int64_t slide,
-                       int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out, int64_t* d_start_out,
-                       int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out, int64_t cap, int64_t* n_out,
-                       void* stream, double* expand_ms) {
+                       int64_t offset, int64_t w0, int64_t w1, int32_t mode, int64_t null_payload, int64_t max_rows,
+                       int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out, int64_t* d_lpay_out,
+                       int64_t* d_rpay_out, uint8_t* d_present_out, int64_t cap, int64_t* n_out, void* stream,
+                       double* expand_ms) {
     JoinGeom g;
     std::string why;
     int rc = join_args(n_l, n_r, size, slide, offset, cap, n_out, g, why);
     if (rc) { set_last_error(why); return rc; }
     *n_out = 0;
     if (expand_ms) *expand_ms = 0;
-    if (n_l == 0 || n_r == 0 || w1 <= w0) return GW_OK;
-    if (!d_lkey || !d_lts || !d_lpay || !d_rkey || !d_rts || !d_rpay ||
+    if (mode < GW_JOIN_MODE_INNER || mode > GW_JOIN_MODE_FULL_OUTER) {
+        set_last_error("window join: unknown mode");
+        return GW_E_INVALID;
+    }
+    // a side without records leaves rows only where the mode keeps the other side's
+    if ((n_l == 0 && !(mode & GW_JOIN_MODE_RIGHT_OUTER)) || (n_r == 0 && !(mode & GW_JOIN_MODE_LEFT_OUTER)) ||
+        n_l + n_r == 0 || w1 <= w0)
+        return GW_OK;
+    if ((n_l > 0 && (!d_lkey || !d_lts || !d_lpay)) || (n_r > 0 && (!d_rkey || !d_rts || !d_rpay)) ||
         (cap > 0 && (!d_key_out || !d_start_out || !d_end_out || !d_lpay_out || !d_rpay_out))) {
         set_last_error("window join: null column");
         return GW_E_INVALID;
@@ -927,10 +1192,10 @@ static int join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts,
     }
     JoinIn a{{d_lkey, d_rkey}, {d_lts, d_rts}, {d_lpay, d_rpay}, n_l, n_l + n_r, g, w0, w1};
     int64_t pairs = 0;
-    rc = join_run(a, [&](int64_t total, JoinOut& o, std::string& w) {
+    rc = join_run(a, mode, null_payload, max_rows, [&](int64_t total, JoinOut& o, std::string& w) {
         *n_out = total;
         if (total > cap) { w = "window join: output arrays too small"; return (int)GW_E_OUTPUT_FULL; }
-        o = JoinOut{{d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out}};
+        o = JoinOut{{d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out}, d_present_out, 0};
         return (int)GW_OK;
     }, &pairs, nullptr, (hipStream_t)stream, why, expand_ms ? &t : nullptr);
     if (expand_ms) {
@@ -948,8 +1213,118 @@ int gw_window_join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_l
                           int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out, int64_t* d_start_out,
                           int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out, int64_t cap, int64_t* n_out,
                           void* stream) {
-    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, d_key_out,
-                       d_start_out, d_end_out, d_lpay_out, d_rpay_out, cap, n_out, stream, nullptr);
+    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1,
+                       GW_JOIN_MODE_INNER, 0, INT64_MAX / 40, d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out,
+                       nullptr, cap, n_out, stream, nullptr);
+}
+
+int gw_window_join_outer_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1, int32_t mode,
+                                int64_t null_payload, int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out,
+                                int64_t* d_lpay_out, int64_t* d_rpay_out, uint8_t* d_present_out, int64_t cap,
+                                int64_t* n_out, void* stream) {
+    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, mode,
+                       null_payload, INT64_MAX / 41, d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out,
+                       d_present_out, cap, n_out, stream, nullptr);
+}
+
+int gw_window_join_outer_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                      int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                      int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1, int32_t mode,
+                                      int64_t null_payload, int64_t* d_key_out, int64_t* d_start_out,
+                                      int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out,
+                                      uint8_t* d_present_out, int64_t cap, int64_t* n_out, void* stream,
+                                      double* expand_ms) {
+    if (!expand_ms) { set_last_error("window join: null expand_ms"); return GW_E_INVALID; }
+    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, mode,
+                       null_payload, INT64_MAX / 41, d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out,
+                       d_present_out, cap, n_out, stream, expand_ms);
+}
+
+// gw_window_cogroup_device, with the time of its two writer kernels in *write_ms when not null.
+static int cogroup_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay, int64_t n_r,
+                          const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay, int64_t size,
+                          int64_t slide, int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out,
+                          int64_t* d_start_out, int64_t* d_end_out, int64_t* d_loff_out, int64_t* d_roff_out,
+                          int64_t* d_lelem_out, int64_t cap_left, int64_t* d_relem_out, int64_t cap_right,
+                          int64_t cap_groups, int64_t* n_out, void* stream, double* write_ms) {
+    JoinGeom g;
+    std::string why;
+    int rc = join_args(n_l, n_r, size, slide, offset, std::min(cap_groups, std::min(cap_left, cap_right)), n_out, g, why);
+    if (rc) { set_last_error(why); return rc; }
+    n_out[0] = n_out[1] = n_out[2] = 0;
+    if (write_ms) *write_ms = 0;
+    if ((n_l > 0 && (!d_lkey || !d_lts || !d_lpay)) || (n_r > 0 && (!d_rkey || !d_rts || !d_rpay)) || !d_loff_out ||
+        !d_roff_out || (cap_groups > 0 && (!d_key_out || !d_start_out || !d_end_out)) || (cap_left > 0 && !d_lelem_out) ||
+        (cap_right > 0 && !d_relem_out)) {
+        set_last_error("window coGroup: null column");
+        return GW_E_INVALID;
+    }
+    if (n_l > INT32_MAX || n_r > INT32_MAX) {
+        set_last_error("window join: more than 2^31 - 1 records on one side");
+        return GW_E_UNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    auto no_groups = [&]() {  // a CSR of no groups: loff[0] = roff[0] = 0
+        hipError_t e = hipMemsetAsync(d_loff_out, 0, 8, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_roff_out, 0, 8, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_last_error(std::string("window coGroup: ") + hipGetErrorString(e)); return (int)GW_E_DEVICE; }
+        return (int)GW_OK;
+    };
+    if (n_l + n_r == 0 || w1 <= w0) return no_groups();
+    JoinTimes t;
+    if (write_ms && (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess)) {
+        if (t.e0) (void)hipEventDestroy(t.e0);
+        set_last_error("window coGroup: hipEventCreate");
+        return GW_E_DEVICE;
+    }
+    JoinIn a{{d_lkey, d_rkey}, {d_lts, d_rts}, {d_lpay, d_rpay}, n_l, n_l + n_r, g, w0, w1};
+    bool wrote = false;
+    rc = cogroup_run(a, [&](int64_t ng, int64_t nl, int64_t nr, CoGroupOut& o, std::string& w) {
+        n_out[0] = ng; n_out[1] = nl; n_out[2] = nr;
+        if (ng > cap_groups || nl > cap_left || nr > cap_right) {
+            w = "window coGroup: output arrays too small";
+            return (int)GW_E_OUTPUT_FULL;
+        }
+        if (ng == 0) return no_groups();
+        o = CoGroupOut{d_key_out, d_start_out, d_end_out, d_loff_out, d_roff_out, d_lelem_out, d_relem_out, 0, 0};
+        wrote = true;
+        return (int)GW_OK;
+    }, n_out, nullptr, s, why, write_ms ? &t : nullptr);
+    if (write_ms) {
+        float ms = 0;
+        if (rc == GW_OK && wrote && hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) *write_ms = ms;
+        (void)hipEventDestroy(t.e0);
+        (void)hipEventDestroy(t.e1);
+    }
+    if (rc) set_last_error(why);
+    return rc;
+}
+
+int gw_window_cogroup_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay, int64_t n_r,
+                             const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay, int64_t size,
+                             int64_t slide, int64_t offset, int64_t w0, int64_t w1, int64_t* d_key_out,
+                             int64_t* d_start_out, int64_t* d_end_out, int64_t* d_loff_out, int64_t* d_roff_out,
+                             int64_t* d_lelem_out, int64_t cap_left, int64_t* d_relem_out, int64_t cap_right,
+                             int64_t cap_groups, int64_t* n_out, void* stream) {
+    return cogroup_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, d_key_out,
+                          d_start_out, d_end_out, d_loff_out, d_roff_out, d_lelem_out, cap_left, d_relem_out, cap_right,
+                          cap_groups, n_out, stream, nullptr);
+}
+
+int gw_window_cogroup_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                   int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                   int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+                                   int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out, int64_t* d_loff_out,
+                                   int64_t* d_roff_out, int64_t* d_lelem_out, int64_t cap_left, int64_t* d_relem_out,
+                                   int64_t cap_right, int64_t cap_groups, int64_t* n_out, void* stream,
+                                   double* write_ms) {
+    if (!write_ms) { set_last_error("window coGroup: null write_ms"); return GW_E_INVALID; }
+    return cogroup_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, d_key_out,
+                          d_start_out, d_end_out, d_loff_out, d_roff_out, d_lelem_out, cap_left, d_relem_out, cap_right,
+                          cap_groups, n_out, stream, write_ms);
 }
 
 int gw_window_join_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
@@ -958,83 +1333,195 @@ int gw_window_join_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_
                                 int64_t* d_start_out, int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out,
                                 int64_t cap, int64_t* n_out, void* stream, double* expand_ms) {
     if (!expand_ms) { set_last_error("window join: null expand_ms"); return GW_E_INVALID; }
-    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1, d_key_out,
-                       d_start_out, d_end_out, d_lpay_out, d_rpay_out, cap, n_out, stream, expand_ms);
+    return join_device(n_l, d_lkey, d_lts, d_lpay, n_r, d_rkey, d_rts, d_rpay, size, slide, offset, w0, w1,
+                       GW_JOIN_MODE_INNER, 0, INT64_MAX / 40, d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out,
+                       nullptr, cap, n_out, stream, expand_ms);
 }
 
-int gw_window_join_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
-                        const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
-                        int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out, int64_t* end_out,
-                        int64_t* lpay_out, int64_t* rpay_out, int64_t cap, int64_t* n_out) {
+}  // extern "C"
+
+// ---- the host entry points ------------------------------------------------------------------
+namespace {
+
+struct HostTup {
+    int64_t start, key, pay;
+    int side;
+};
+// The (record, fired window) tuples of both sides sorted into groups: windows ascending, keys
+// ascending, left before right, each side in arrival order.
+int host_tuples(const JoinGeom& g, int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t w0, int64_t w1,
+                std::vector<HostTup>& t) {
+    const int64_t* keys[2] = {lkey, rkey};
+    const int64_t* tss[2] = {lts, rts};
+    const int64_t* pays[2] = {lpay, rpay};
+    const int64_t ns[2] = {n_l, n_r};
+    for (int side = 0; side < 2; ++side)
+        for (int64_t i = 0; i < ns[side]; ++i) {
+            int64_t ls;
+            int nw;
+            const unsigned f = join_windows(g, tss[side][i], ls, nw);
+            if (f & GW_DF_NO_TS) {
+                set_last_error("Record has Long.MIN_VALUE timestamp (= no timestamp marker)");
+                return GW_E_NO_TIMESTAMP;
+            }
+            if (f) { set_last_error("window join: window bounds overflow int64"); return GW_E_RANGE; }
+            uint64_t m = join_fired(g, ls, nw, w0, w1);
+            for (int k = 0; m; ++k, m >>= 1)
+                if (m & 1) t.push_back({ls - (int64_t)k * g.slide, keys[side][i], pays[side][i], side});
+        }
+    if ((int64_t)t.size() > kSortMaxRecords) {
+        set_last_error("window join: more than 2^30 - 1 (record, fired window) tuples in one fire");
+        return GW_E_UNSUPPORTED;
+    }
+    // left tuples were made first, each side in arrival order: stability keeps both
+    std::stable_sort(t.begin(), t.end(), [](const HostTup& x, const HostTup& y) {
+        return x.start != y.start ? x.start < y.start : x.key < y.key;
+    });
+    return GW_OK;
+}
+// The group starting at tuple i: its end and its number of left tuples.
+size_t host_group(const std::vector<HostTup>& t, size_t i, size_t& l) {
+    size_t j = i;
+    l = 0;
+    for (; j < t.size() && t[j].start == t[i].start && t[j].key == t[i].key; ++j) l += t[j].side == 0;
+    return j;
+}
+
+int join_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r, const int64_t* rkey,
+              const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+              int32_t mode, int64_t null_payload, int64_t max_rows, int64_t* key_out, int64_t* start_out, int64_t* end_out,
+              int64_t* lpay_out, int64_t* rpay_out, uint8_t* present_out, int64_t cap, int64_t* n_out) {
     JoinGeom g;
     std::string why;
     int rc = join_args(n_l, n_r, size, slide, offset, cap, n_out, g, why);
     if (rc) { set_last_error(why); return rc; }
     *n_out = 0;
-    if (n_l == 0 || n_r == 0 || w1 <= w0) return GW_OK;
-    if (!lkey || !lts || !lpay || !rkey || !rts || !rpay ||
+    if (mode < GW_JOIN_MODE_INNER || mode > GW_JOIN_MODE_FULL_OUTER) {
+        set_last_error("window join: unknown mode");
+        return GW_E_INVALID;
+    }
+    const bool keep_l = mode & GW_JOIN_MODE_LEFT_OUTER, keep_r = mode & GW_JOIN_MODE_RIGHT_OUTER;
+    if ((n_l == 0 && !keep_r) || (n_r == 0 && !keep_l) || n_l + n_r == 0 || w1 <= w0) return GW_OK;
+    if ((n_l > 0 && (!lkey || !lts || !lpay)) || (n_r > 0 && (!rkey || !rts || !rpay)) ||
         (cap > 0 && (!key_out || !start_out || !end_out || !lpay_out || !rpay_out))) {
         set_last_error("window join: null column");
         return GW_E_INVALID;
     }
     try {
-        struct Tup {
-            int64_t start, key, pay;
-            int side;
-        };
-        std::vector<Tup> t;
-        const int64_t* keys[2] = {lkey, rkey};
-        const int64_t* tss[2] = {lts, rts};
-        const int64_t* pays[2] = {lpay, rpay};
-        const int64_t ns[2] = {n_l, n_r};
-        for (int side = 0; side < 2; ++side)
-            for (int64_t i = 0; i < ns[side]; ++i) {
-                int64_t ls;
-                int nw;
-                const unsigned f = join_windows(g, tss[side][i], ls, nw);
-                if (f & GW_DF_NO_TS) {
-                    set_last_error("Record has Long.MIN_VALUE timestamp (= no timestamp marker)");
-                    return GW_E_NO_TIMESTAMP;
-                }
-                if (f) { set_last_error("window join: window bounds overflow int64"); return GW_E_RANGE; }
-                uint64_t m = join_fired(g, ls, nw, w0, w1);
-                for (int k = 0; m; ++k, m >>= 1)
-                    if (m & 1) t.push_back({ls - (int64_t)k * g.slide, keys[side][i], pays[side][i], side});
-            }
-        if ((int64_t)t.size() > kSortMaxRecords) {
-            set_last_error("window join: more than 2^30 - 1 (record, fired window) tuples in one fire");
-            return GW_E_UNSUPPORTED;
-        }
-        // left tuples were made first, each side in arrival order: stability keeps both
-        std::stable_sort(t.begin(), t.end(), [](const Tup& x, const Tup& y) {
-            return x.start != y.start ? x.start < y.start : x.key < y.key;
-        });
+        std::vector<HostTup> t;
+        if ((rc = host_tuples(g, n_l, lkey, lts, lpay, n_r, rkey, rts, rpay, w0, w1, t))) return rc;
         const size_t n = t.size();
+        auto rows = [&](size_t l, size_t r) -> __int128 {
+            if (l && r) return (__int128)l * (__int128)r;
+            return l ? (keep_l ? l : 0) : (keep_r ? r : 0);
+        };
         __int128 total = 0;
-        for (size_t i = 0; i < n;) {
-            size_t j = i, l = 0;
-            for (; j < n && t[j].start == t[i].start && t[j].key == t[i].key; ++j) l += t[j].side == 0;
-            total += (__int128)l * (__int128)(j - i - l);
+        for (size_t i = 0, l; i < n;) {
+            const size_t j = host_group(t, i, l);
+            total += rows(l, j - i - l);
             i = j;
         }
-        if (total > (__int128)(INT64_MAX / 40)) {
+        if (total > (__int128)max_rows) {
             set_last_error("window join: the pairs of one fire exceed int64 bytes");
             return GW_E_RANGE;
         }
         *n_out = (int64_t)total;
         if ((int64_t)total > cap) { set_last_error("window join: output arrays too small"); return GW_E_OUTPUT_FULL; }
         int64_t o = 0;
-        for (size_t i = 0; i < n;) {
-            size_t j = i, l = 0;
-            for (; j < n && t[j].start == t[i].start && t[j].key == t[i].key; ++j) l += t[j].side == 0;
-            for (size_t x = i; x < i + l; ++x)
-                for (size_t y = i + l; y < j; ++y, ++o) {
-                    key_out[o] = t[i].key;
-                    start_out[o] = t[i].start;
-                    end_out[o] = t[i].start + g.size;
-                    lpay_out[o] = t[x].pay;
-                    rpay_out[o] = t[y].pay;
-                }
+        auto row = [&](const HostTup& h, const HostTup* x, const HostTup* y) {
+            key_out[o] = h.key;
+            start_out[o] = h.start;
+            end_out[o] = h.start + g.size;
+            lpay_out[o] = x ? x->pay : null_payload;
+            rpay_out[o] = y ? y->pay : null_payload;
+            if (present_out) present_out[o] = (uint8_t)((x ? 1 : 0) | (y ? 2 : 0));
+            ++o;
+        };
+        for (size_t i = 0, l; i < n;) {
+            const size_t j = host_group(t, i, l);
+            if (rows(l, j - i - l) > 0) {
+                if (l == 0)
+                    for (size_t y = i; y < j; ++y) row(t[i], nullptr, &t[y]);
+                else if (l == j - i)
+                    for (size_t x = i; x < j; ++x) row(t[i], &t[x], nullptr);
+                else
+                    for (size_t x = i; x < i + l; ++x)
+                        for (size_t y = i + l; y < j; ++y) row(t[i], &t[x], &t[y]);
+            }
+            i = j;
+        }
+    } catch (const std::bad_alloc&) {
+        set_last_error("window join: out of host memory");
+        return GW_E_OOM;
+    }
+    return GW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gw_window_join_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                        const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
+                        int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out, int64_t* end_out,
+                        int64_t* lpay_out, int64_t* rpay_out, int64_t cap, int64_t* n_out) {
+    return join_host(n_l, lkey, lts, lpay, n_r, rkey, rts, rpay, size, slide, offset, w0, w1, GW_JOIN_MODE_INNER, 0,
+                     INT64_MAX / 40, key_out, start_out, end_out, lpay_out, rpay_out, nullptr, cap, n_out);
+}
+
+int gw_window_join_outer_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                              const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
+                              int64_t offset, int64_t w0, int64_t w1, int32_t mode, int64_t null_payload,
+                              int64_t* key_out, int64_t* start_out, int64_t* end_out, int64_t* lpay_out,
+                              int64_t* rpay_out, uint8_t* present_out, int64_t cap, int64_t* n_out) {
+    return join_host(n_l, lkey, lts, lpay, n_r, rkey, rts, rpay, size, slide, offset, w0, w1, mode, null_payload,
+                     INT64_MAX / 41, key_out, start_out, end_out, lpay_out, rpay_out, present_out, cap, n_out);
+}
+
+int gw_window_cogroup_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                           const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
+                           int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out,
+                           int64_t* end_out, int64_t* loff_out, int64_t* roff_out, int64_t* lelem_out, int64_t cap_left,
+                           int64_t* relem_out, int64_t cap_right, int64_t cap_groups, int64_t* n_out) {
+    JoinGeom g;
+    std::string why;
+    int rc = join_args(n_l, n_r, size, slide, offset, std::min(cap_groups, std::min(cap_left, cap_right)), n_out, g, why);
+    if (rc) { set_last_error(why); return rc; }
+    n_out[0] = n_out[1] = n_out[2] = 0;
+    if ((n_l > 0 && (!lkey || !lts || !lpay)) || (n_r > 0 && (!rkey || !rts || !rpay)) || !loff_out || !roff_out ||
+        (cap_groups > 0 && (!key_out || !start_out || !end_out)) || (cap_left > 0 && !lelem_out) ||
+        (cap_right > 0 && !relem_out)) {
+        set_last_error("window coGroup: null column");
+        return GW_E_INVALID;
+    }
+    try {
+        std::vector<HostTup> t;
+        if (w1 > w0 && (rc = host_tuples(g, n_l, lkey, lts, lpay, n_r, rkey, rts, rpay, w0, w1, t))) return rc;
+        const size_t n = t.size();
+        int64_t ng = 0, nl = 0;
+        for (size_t i = 0, l; i < n; ++ng) {
+            i = host_group(t, i, l);
+            nl += (int64_t)l;
+        }
+        n_out[0] = ng;
+        n_out[1] = nl;
+        n_out[2] = (int64_t)n - nl;
+        if (ng > cap_groups || n_out[1] > cap_left || n_out[2] > cap_right) {
+            set_last_error("window coGroup: output arrays too small");
+            return GW_E_OUTPUT_FULL;
+        }
+        int64_t gi = 0, lo = 0, ro = 0;
+        loff_out[0] = roff_out[0] = 0;
+        for (size_t i = 0, l; i < n; ++gi) {
+            const size_t j = host_group(t, i, l);
+            key_out[gi] = t[i].key;
+            start_out[gi] = t[i].start;
+            end_out[gi] = t[i].start + g.size;
+            for (size_t x = i; x < i + l; ++x) lelem_out[lo++] = t[x].pay;
+            for (size_t y = i + l; y < j; ++y) relem_out[ro++] = t[y].pay;
+            loff_out[gi + 1] = lo;
+            roff_out[gi + 1] = ro;
             i = j;
         }
     } catch (const std::bad_alloc&) {
@@ -1103,6 +1590,7 @@ int gw_join_ingest_device(gw_join* h, int32_t side, int64_t n, const int64_t* d_
     JOIN_ENTER(h);
     if ((side != 0 && side != 1) || n < 0 || (n > 0 && (!d_key || !d_ts || !d_payload)))
         return h->fail(GW_E_INVALID, "gw_join_ingest_device: bad side or null column");
+    h->touched = true;
     if (n + h->n_log[side] > INT32_MAX) return h->fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
     hipStream_t ps = (hipStream_t)stream;
     if (ps != h->stream) {
@@ -1122,6 +1610,7 @@ int gw_join_ingest(gw_join* h, int32_t side, int64_t n, const int64_t* key, cons
     JOIN_ENTER(h);
     if ((side != 0 && side != 1) || n < 0 || (n > 0 && (!key || !ts || !payload)))
         return h->fail(GW_E_INVALID, "gw_join_ingest: bad side or null column");
+    h->touched = true;
     if (n + h->n_log[side] > INT32_MAX) return h->fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
     for (int64_t at = 0; at < n; at += h->max_batch) {
         const int64_t m = std::min(h->max_batch, n - at);
@@ -1151,16 +1640,35 @@ int gw_join_end_input(gw_join* h, int64_t* pairs_fired) {
     return h->advance(INT64_MAX, pairs_fired);
 }
 
+int gw_join_set_mode(gw_join* h, int32_t mode, int64_t null_payload) {
+    JOIN_ENTER(h);
+    if (mode < GW_JOIN_MODE_INNER || mode > GW_JOIN_MODE_COGROUP) return h->fail(GW_E_INVALID, "gw_join_set_mode: unknown mode");
+    if (h->touched) {  // (not a failure of the handle: it goes on in the mode it has)
+        h->err = "gw_join_set_mode: only before the first ingest or watermark";
+        return GW_E_STATE;
+    }
+    h->mode = mode;
+    h->null_payload = null_payload;
+    return GW_OK;
+}
+
+#define JOIN_PAIRS(h, what)                                                                          \
+    if ((h)->mode == GW_JOIN_MODE_COGROUP) return (h)->fail(GW_E_INVALID, what ": the handle is in coGroup mode")
+#define JOIN_COGROUP(h, what)                                                                        \
+    if ((h)->mode != GW_JOIN_MODE_COGROUP) return (h)->fail(GW_E_INVALID, what ": the handle is not in coGroup mode")
+
 int gw_join_pending(gw_join* h, int64_t* n) {
     JOIN_ENTER(h);
+    JOIN_PAIRS(h, "gw_join_pending");
     if (!n) return h->fail(GW_E_INVALID, "gw_join_pending: null argument");
     *n = h->pending;
     return GW_OK;
 }
 
-int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay, int64_t cap,
-                  int64_t* n) {
+int gw_join_drain_outer(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay,
+                        uint8_t* present, int64_t cap, int64_t* n) {
     JOIN_ENTER(h);
+    JOIN_PAIRS(h, "gw_join_drain");
     if (!n || cap < 0 || (cap > 0 && (!key || !start || !end || !lpay || !rpay)))
         return h->fail(GW_E_INVALID, "gw_join_drain: bad argument");
     const int64_t m = std::min(cap, h->pending);
@@ -1169,6 +1677,8 @@ int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_
     hipError_t e = hipSuccess;
     for (int c = 0; c < 5 && m > 0 && e == hipSuccess; ++c)
         e = hipMemcpyAsync(dst[c], h->out[c] + h->out_from, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream);
+    if (present && m > 0 && e == hipSuccess)
+        e = hipMemcpyAsync(present, h->pres.p + h->out_from, (size_t)m, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return h->dev_fail(e);
     h->out_from += m;
@@ -1177,13 +1687,74 @@ int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_
     return h->pending > 0 ? GW_E_OUTPUT_FULL : GW_OK;
 }
 
-int gw_join_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
-                        const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n) {
+int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay, int64_t cap,
+                  int64_t* n) {
+    return gw_join_drain_outer(h, key, start, end, lpay, rpay, nullptr, cap, n);
+}
+
+int gw_join_rows_device_outer(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                              const int64_t** d_lpay, const int64_t** d_rpay, const uint8_t** d_present, int64_t* n) {
     JOIN_ENTER(h);
+    JOIN_PAIRS(h, "gw_join_rows_device");
     if (!d_key || !d_start || !d_end || !d_lpay || !d_rpay || !n) return h->fail(GW_E_INVALID, "gw_join_rows_device: null argument");
     const int64_t** dst[5] = {d_key, d_start, d_end, d_lpay, d_rpay};
     for (int c = 0; c < 5; ++c) *dst[c] = h->pending ? h->out[c] + h->out_from : nullptr;
+    if (d_present) *d_present = h->pending ? h->pres.p + h->out_from : nullptr;
     *n = h->pending;
+    return GW_OK;
+}
+
+int gw_join_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                        const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n) {
+    return gw_join_rows_device_outer(h, d_key, d_start, d_end, d_lpay, d_rpay, nullptr, n);
+}
+
+int gw_join_cogroup_pending(gw_join* h, int64_t* n) {
+    JOIN_ENTER(h);
+    JOIN_COGROUP(h, "gw_join_cogroup_pending");
+    if (!n) return h->fail(GW_E_INVALID, "gw_join_cogroup_pending: null argument");
+    for (int c = 0; c < 3; ++c) n[c] = h->cg_n[c];
+    return GW_OK;
+}
+
+int gw_join_cogroup_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* loff, int64_t* roff,
+                          int64_t* lelem, int64_t cap_left, int64_t* relem, int64_t cap_right, int64_t cap_groups,
+                          int64_t* n) {
+    JOIN_ENTER(h);
+    JOIN_COGROUP(h, "gw_join_cogroup_drain");
+    const int64_t* m = h->cg_n;
+    if (!n || cap_groups < 0 || cap_left < 0 || cap_right < 0 || !loff || !roff ||
+        (cap_groups > 0 && (!key || !start || !end)) || (cap_left > 0 && !lelem) || (cap_right > 0 && !relem))
+        return h->fail(GW_E_INVALID, "gw_join_cogroup_drain: bad argument");
+    for (int c = 0; c < 3; ++c) n[c] = m[c];
+    if (m[0] > cap_groups || m[1] > cap_left || m[2] > cap_right)
+        return h->fail(GW_E_OUTPUT_FULL, "gw_join_cogroup_drain: output arrays too small");
+    loff[0] = roff[0] = 0;
+    if (m[0] == 0) return GW_OK;
+    int64_t* dst[5] = {key, start, end, loff, roff};
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < 5 && e == hipSuccess; ++c)
+        e = hipMemcpyAsync(dst[c], h->cg[c], (size_t)(m[0] + (c >= 3)) * 8, hipMemcpyDeviceToHost, h->stream);
+    if (m[1] > 0 && e == hipSuccess) e = hipMemcpyAsync(lelem, h->cg_elem[0][0], (size_t)m[1] * 8, hipMemcpyDeviceToHost, h->stream);
+    if (m[2] > 0 && e == hipSuccess) e = hipMemcpyAsync(relem, h->cg_elem[1][0], (size_t)m[2] * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return h->dev_fail(e);
+    h->cg_n[0] = h->cg_n[1] = h->cg_n[2] = 0;
+    return GW_OK;
+}
+
+int gw_join_cogroup_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                                const int64_t** d_loff, const int64_t** d_roff, const int64_t** d_lelem,
+                                const int64_t** d_relem, int64_t* n) {
+    JOIN_ENTER(h);
+    JOIN_COGROUP(h, "gw_join_cogroup_rows_device");
+    if (!d_key || !d_start || !d_end || !d_loff || !d_roff || !d_lelem || !d_relem || !n)
+        return h->fail(GW_E_INVALID, "gw_join_cogroup_rows_device: null argument");
+    const int64_t** dst[5] = {d_key, d_start, d_end, d_loff, d_roff};
+    for (int c = 0; c < 5; ++c) *dst[c] = h->cg_n[0] ? h->cg[c] : nullptr;
+    *d_lelem = h->cg_n[1] ? h->cg_elem[0][0] : nullptr;
+    *d_relem = h->cg_n[2] ? h->cg_elem[1][0] : nullptr;
+    for (int c = 0; c < 3; ++c) n[c] = h->cg_n[c];
     return GW_OK;
 }
 
@@ -1191,6 +1762,7 @@ int gw_join_clear_rows(gw_join* h) {
     JOIN_ENTER(h);
     h->pending = 0;
     h->out_from = 0;
+    h->cg_n[0] = h->cg_n[1] = h->cg_n[2] = 0;
     return GW_OK;
 }
 

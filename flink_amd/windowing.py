@@ -20,6 +20,7 @@ Every call goes to the HIP library; there is no CPU path here.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import struct
 import time
@@ -388,6 +389,125 @@ def window_join_host(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner,
         N.check(rc)
         break
     return tuple(o[:n_out.value] for o in out)
+
+
+def _join_mode(mode, cogroup_ok=False) -> int:
+    """A GW_JOIN_MODE_* from its number or its name ("inner", "left_outer", "right_outer",
+    "full_outer", and for the operator "cogroup")."""
+    m = N.JOIN_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= (N.JOIN_MODE_COGROUP if cogroup_ok else 3):
+        raise ValueError(f"unknown join mode {mode!r}")
+    return m
+
+
+def window_join_outer_device(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner, mode="full_outer",
+                             null_payload: int = 0, w0: int = LONG_MIN, w1: int = LONG_MAX, stream=None,
+                             present: bool = True):
+    """gw_window_join_outer_device over torch device tensors: window_join_device in an outer mode.
+    Per fired (window, key) the cross product of the two sides, or where one side is empty and the
+    mode keeps the other, that side's records with null_payload in the lacking column.  Returns
+    (key, start, end, left payload, right payload, present); present (uint8: 1 left only, 2 right
+    only, 3 both) is None with present=False."""
+    import torch
+    _, size, slide, offset = _join_geometry(assigner)
+    mode = _join_mode(mode)
+    dev = lkey.device if lkey.numel() else rkey.device
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    n_out = ctypes.c_int64(0)
+    cap = max(lkey.numel(), rkey.numel(), 1)
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    while True:
+        out = [torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(5)]
+        pres = torch.empty(cap, dtype=torch.uint8, device=dev) if present else None
+        rc = N.lib().gw_window_join_outer_device(lkey.numel(), P(lkey), P(lts), P(lpay), rkey.numel(), P(rkey), P(rts),
+                                                 P(rpay), size, slide, offset, int(w0), int(w1), mode, int(null_payload),
+                                                 *[o.data_ptr() for o in out], pres.data_ptr() if present else None, cap,
+                                                 ctypes.byref(n_out), ctypes.c_void_p(stream) if stream else None)
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    return tuple(o[:n_out.value] for o in out) + (pres[:n_out.value] if present else None,)
+
+
+def window_join_outer_host(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner, mode="full_outer",
+                           null_payload: int = 0, w0: int = LONG_MIN, w1: int = LONG_MAX):
+    """gw_window_join_outer_host over numpy columns: window_join_outer_device as plain host code."""
+    _, size, slide, offset = _join_geometry(assigner)
+    mode = _join_mode(mode)
+    cols = [np.ascontiguousarray(x, dtype=np.int64) for x in (lkey, lts, lpay, rkey, rts, rpay)]
+    if not (len(cols[0]) == len(cols[1]) == len(cols[2]) and len(cols[3]) == len(cols[4]) == len(cols[5])):
+        raise ValueError("column lengths differ")
+    n_out = ctypes.c_int64(0)
+    cap = max(len(cols[0]), len(cols[3]), 1)
+    while True:
+        out = [np.empty(cap, np.int64) for _ in range(5)]
+        pres = np.empty(cap, np.uint8)
+        rc = N.lib().gw_window_join_outer_host(len(cols[0]), *[_ptr(c) for c in cols[:3]], len(cols[3]),
+                                               *[_ptr(c) for c in cols[3:]], size, slide, offset, int(w0), int(w1), mode,
+                                               int(null_payload), *[_ptr(o) for o in out], _ptr(pres), cap,
+                                               ctypes.byref(n_out))
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    return tuple(o[:n_out.value] for o in out) + (pres[:n_out.value],)
+
+
+def window_cogroup_device(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner, w0: int = LONG_MIN,
+                          w1: int = LONG_MAX, stream=None):
+    """gw_window_cogroup_device over torch device tensors: every fired (window, key) with a record
+    on either side as a CSR.  Returns device tensors (key, start, end, loff, roff, lelem, relem):
+    group g's left payloads are lelem[loff[g]:loff[g + 1]] in arrival order, likewise right; what
+    CoGroupFunction.coGroup is called with, in the join's order."""
+    import torch
+    _, size, slide, offset = _join_geometry(assigner)
+    dev = lkey.device if lkey.numel() else rkey.device
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    n = (ctypes.c_int64 * 3)()
+    caps = [max(lkey.numel() + rkey.numel(), 1), max(lkey.numel(), 1), max(rkey.numel(), 1)]
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    while True:
+        E = lambda k: torch.empty(k, dtype=torch.int64, device=dev)
+        g = [E(caps[0]) for _ in range(3)] + [E(caps[0] + 1) for _ in range(2)]
+        le, re = E(caps[1]), E(caps[2])
+        rc = N.lib().gw_window_cogroup_device(lkey.numel(), P(lkey), P(lts), P(lpay), rkey.numel(), P(rkey), P(rts), P(rpay),
+                                              size, slide, offset, int(w0), int(w1), *[x.data_ptr() for x in g],
+                                              le.data_ptr(), caps[1], re.data_ptr(), caps[2], caps[0], n,
+                                              ctypes.c_void_p(stream) if stream else None)
+        if rc == N.GW_E_OUTPUT_FULL and any(n[i] > caps[i] for i in range(3)):
+            caps = [max(caps[i], n[i]) for i in range(3)]
+            continue
+        N.check(rc)
+        break
+    return (g[0][:n[0]], g[1][:n[0]], g[2][:n[0]], g[3][:n[0] + 1], g[4][:n[0] + 1], le[:n[1]], re[:n[2]])
+
+
+def window_cogroup_host(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssigner, w0: int = LONG_MIN,
+                        w1: int = LONG_MAX):
+    """gw_window_cogroup_host over numpy columns: window_cogroup_device as plain host code."""
+    _, size, slide, offset = _join_geometry(assigner)
+    cols = [np.ascontiguousarray(x, dtype=np.int64) for x in (lkey, lts, lpay, rkey, rts, rpay)]
+    if not (len(cols[0]) == len(cols[1]) == len(cols[2]) and len(cols[3]) == len(cols[4]) == len(cols[5])):
+        raise ValueError("column lengths differ")
+    n = (ctypes.c_int64 * 3)()
+    caps = [max(len(cols[0]) + len(cols[3]), 1), max(len(cols[0]), 1), max(len(cols[3]), 1)]
+    while True:
+        g = [np.empty(caps[0], np.int64) for _ in range(3)] + [np.empty(caps[0] + 1, np.int64) for _ in range(2)]
+        le, re = np.empty(caps[1], np.int64), np.empty(caps[2], np.int64)
+        rc = N.lib().gw_window_cogroup_host(len(cols[0]), *[_ptr(c) for c in cols[:3]], len(cols[3]),
+                                            *[_ptr(c) for c in cols[3:]], size, slide, offset, int(w0), int(w1),
+                                            *[_ptr(x) for x in g], _ptr(le), caps[1], _ptr(re), caps[2], caps[0], n)
+        if rc == N.GW_E_OUTPUT_FULL and any(n[i] > caps[i] for i in range(3)):
+            caps = [max(caps[i], n[i]) for i in range(3)]
+            continue
+        N.check(rc)
+        break
+    return (g[0][:n[0]], g[1][:n[0]], g[2][:n[0]], g[3][:n[0] + 1], g[4][:n[0] + 1], le[:n[1]], re[:n[2]])
 
 
 # ------------------------------------------------------------------------ operator
@@ -1162,12 +1282,19 @@ class GpuWindowJoinOperator:
     WindowOperator with ListState -> JoinCoGroupFunction.  Records are (key, ts, payload) int64
     columns per side (payload: the element as the caller numbers or packs it); a fire leaves
     (key, start, end, left payload, right payload) pairs, windows by ascending end, keys ascending,
-    left-major in arrival order.  Tumbling and sliding event-time windows, allowed lateness 0."""
+    left-major in arrival order.  Tumbling and sliding event-time windows, allowed lateness 0.
+    mode: "inner" (default), "left_outer", "right_outer", "full_outer" -- the unmatched records of
+    the kept sides come as rows with null_payload in the lacking column, drain_outer() adds the
+    present column -- or "cogroup": a fire leaves the groups themselves, one-sided ones included,
+    as a CSR (cogroup_drain, cogroup_rows_device)."""
 
     LEFT, RIGHT = N.JOIN_LEFT, N.JOIN_RIGHT
 
-    def __init__(self, assigner: WindowAssigner, device: int = 0, capacity_hint: int = 0, max_batch: int = 0):
+    def __init__(self, assigner: WindowAssigner, device: int = 0, capacity_hint: int = 0, max_batch: int = 0,
+                 mode="inner", null_payload: int = 0):
         self.assigner = assigner
+        self.mode = _join_mode(mode, cogroup_ok=True)
+        self.null_payload = int(null_payload)
         c = N.GwJoinConfig()
         c.assigner, c.size, c.slide, c.offset = _join_geometry(assigner)
         c.device, c.capacity_hint, c.max_batch = device, capacity_hint, max_batch
@@ -1181,7 +1308,15 @@ class GpuWindowJoinOperator:
             raise ValueError(N.lib().gw_last_error(None).decode())
         N.check(rc, None)
         self._h = h
+        if self.mode != N.JOIN_MODE_INNER:
+            self.set_mode(self.mode, self.null_payload)
         return self
+
+    def set_mode(self, mode, null_payload: int = 0):
+        """gw_join_set_mode: only before the first batch or watermark (GW_E_STATE afterwards)."""
+        m = _join_mode(mode, cogroup_ok=True)
+        self._check(N.lib().gw_join_set_mode(self._h, m, int(null_payload)))
+        self.mode, self.null_payload = m, int(null_payload)
 
     def close(self):
         if self._h:
@@ -1259,12 +1394,62 @@ class GpuWindowJoinOperator:
         assert at == n
         return tuple(out)
 
+    def drain_outer(self, cap: Optional[int] = None):
+        """drain() with the present column (uint8: 1 left only, 2 right only, 3 both) as a sixth."""
+        n = self.pending()
+        out = [np.empty(n, np.int64) for _ in range(5)]
+        pres = np.empty(n, np.uint8)
+        step = n if cap is None else max(1, int(cap))
+        at = 0
+        got = ctypes.c_int64(0)
+        while at < n:
+            rc = N.lib().gw_join_drain_outer(self._h, *[ctypes.c_void_p(o.ctypes.data + 8 * at) for o in out],
+                                             ctypes.c_void_p(pres.ctypes.data + at), step, ctypes.byref(got))
+            if rc != N.GW_E_OUTPUT_FULL:
+                self._check(rc)
+            at += got.value
+            if rc == N.GW_OK:
+                break
+        assert at == n
+        return tuple(out) + (pres,)
+
     def rows_device(self):
         """Zero-copy view of the pending pairs: five device pointers and their number."""
         p = [ctypes.c_void_p() for _ in range(5)]
         n = ctypes.c_int64(0)
         self._check(N.lib().gw_join_rows_device(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
         return [x.value for x in p], n.value
+
+    def rows_device_outer(self):
+        """rows_device() with the present column's pointer as a sixth."""
+        p = [ctypes.c_void_p() for _ in range(6)]
+        n = ctypes.c_int64(0)
+        self._check(N.lib().gw_join_rows_device_outer(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
+        return [x.value for x in p], n.value
+
+    def cogroup_pending(self):
+        """(groups, left elements, right elements) pending in coGroup mode."""
+        n = (ctypes.c_int64 * 3)()
+        self._check(N.lib().gw_join_cogroup_pending(self._h, n))
+        return tuple(n)
+
+    def cogroup_drain(self):
+        """The pending groups of every fire since the last drain as one CSR, numpy (key, start,
+        end, loff, roff, lelem, relem): group g's left payloads are lelem[loff[g]:loff[g + 1]]."""
+        ng, nl, nr = self.cogroup_pending()
+        g = [np.empty(ng, np.int64) for _ in range(3)] + [np.empty(ng + 1, np.int64) for _ in range(2)]
+        le, re = np.empty(nl, np.int64), np.empty(nr, np.int64)
+        n = (ctypes.c_int64 * 3)()
+        self._check(N.lib().gw_join_cogroup_drain(self._h, *[_ptr(x) for x in g], _ptr(le), nl, _ptr(re), nr, ng, n))
+        return tuple(g) + (le, re)
+
+    def cogroup_rows_device(self):
+        """Zero-copy view of the pending CSR: seven device pointers (key, start, end, loff, roff,
+        lelem, relem) and (groups, left elements, right elements)."""
+        p = [ctypes.c_void_p() for _ in range(7)]
+        n = (ctypes.c_int64 * 3)()
+        self._check(N.lib().gw_join_cogroup_rows_device(self._h, *[ctypes.byref(x) for x in p], n))
+        return [x.value for x in p], tuple(n)
 
     def clear_rows(self):
         self._check(N.lib().gw_join_clear_rows(self._h))
@@ -1324,6 +1509,17 @@ class JoinedStreams:
         get ids in their sorted order, so "keys ascending" is the keys' own order."""
         if self._fn is None:
             raise ValueError("apply() before execute_and_collect()")
+        out = []
+        with self._run() as (op, lefts, rights):
+            _, _, e, lp, rp = op.drain()
+            for i in range(len(e)):
+                out.append(StreamRecord(self._fn(lefts[int(lp[i])].value, rights[int(rp[i])].value), int(e[i]) - 1))
+        return out
+
+    @contextlib.contextmanager
+    def _run(self, **mode):
+        """Both bounded sources through one operator to the end of input: yields (operator, left
+        records, right records); a record's payload is its index in its side's list."""
         lefts = [e for e in self.left.elements if isinstance(e, StreamRecord)]
         rights = [e for e in self.right.elements if isinstance(e, StreamRecord)]
         keys_in, keys_out = {}, []
@@ -1341,9 +1537,8 @@ class JoinedStreams:
             for k in sorted(set(allk), key=lambda k: (type(k).__name__, k)):
                 kid(k)
         enc = (lambda k: k) if int_keys else kid
-        out = []
         kw = {k: v for k, v in self.left.env.op_kwargs.items() if k in ("device", "capacity_hint", "max_batch")}
-        with GpuWindowJoinOperator(self.assigner, **kw) as op:
+        with GpuWindowJoinOperator(self.assigner, **kw, **mode) as op:
             # the two-input operator's watermark is the minimum of its inputs' (AbstractStreamOperator
             # .processWatermark1/2): with each bounded source fed whole, the first one is end of input
             for side, elems, sel in ((op.LEFT, lefts, self._k1), (op.RIGHT, rights, self._k2)):
@@ -1351,9 +1546,49 @@ class JoinedStreams:
                     op.process_batch(side, [enc(sel(e.value)) for e in elems], [int(e.timestamp) for e in elems],
                                      list(range(len(elems))))
             op.end_input()
-            _, _, e, lp, rp = op.drain()
-            for i in range(len(e)):
-                out.append(StreamRecord(self._fn(lefts[int(lp[i])].value, rights[int(rp[i])].value), int(e[i]) - 1))
+            yield op, lefts, rights
+
+
+class OuterJoin:
+    """A CoGroupFunction of the closed set that runs wholly on the device: the left, right or full
+    outer join.  CoGroupedStreams.apply(OuterJoin(kind, fn)) runs the operator in that outer mode
+    and calls fn(left_or_None, right_or_None) per row, so no per-group lists are built."""
+
+    KINDS = {"left": N.JOIN_MODE_LEFT_OUTER, "right": N.JOIN_MODE_RIGHT_OUTER, "full": N.JOIN_MODE_FULL_OUTER}
+
+    def __init__(self, kind: str, join_function: Callable):
+        if kind not in self.KINDS:
+            raise ValueError("OuterJoin kind: 'left', 'right' or 'full'")
+        self.kind, self.mode, self.fn = kind, self.KINDS[kind], join_function
+
+
+class CoGroupedStreams(JoinedStreams):
+    """stream.co_group(other) -- CoGroupedStreams (RS/api/datastream/CoGroupedStreams.java): where(k1)
+    .equal_to(k2).window(assigner).apply(co_group_function).execute_and_collect().
+    co_group_function(lefts, rights) is called once per fired (window, key) with a record on either
+    side, one list possibly empty, and returns an iterable of outputs; an OuterJoin runs as rows."""
+
+    def execute_and_collect(self) -> list:
+        """The outputs as StreamRecords with timestamp end - 1, groups in the operator's order
+        (windows by ascending end, keys ascending), each side's elements in arrival order."""
+        if self._fn is None:
+            raise ValueError("apply() before execute_and_collect()")
+        out = []
+        if isinstance(self._fn, OuterJoin):
+            with self._run(mode=self._fn.mode, null_payload=-1) as (op, lefts, rights):
+                _, _, e, lp, rp, pres = op.drain_outer()
+                for i in range(len(e)):
+                    l = lefts[int(lp[i])].value if pres[i] & 1 else None
+                    r = rights[int(rp[i])].value if pres[i] & 2 else None
+                    out.append(StreamRecord(self._fn.fn(l, r), int(e[i]) - 1))
+            return out
+        with self._run(mode="cogroup") as (op, lefts, rights):
+            _, _, e, loff, roff, le, re = op.cogroup_drain()
+            for g in range(len(e)):
+                ls = [lefts[int(i)].value for i in le[loff[g]:loff[g + 1]]]
+                rs = [rights[int(i)].value for i in re[roff[g]:roff[g + 1]]]
+                for v in self._fn(ls, rs):
+                    out.append(StreamRecord(v, int(e[g]) - 1))
         return out
 
 
@@ -1518,6 +1753,12 @@ class DataStream:
     def join(self, other: "DataStream") -> JoinedStreams:
         """DataStream.join (RS/api/datastream/DataStream.java): a window join with `other`."""
         return JoinedStreams(self, other)
+
+    def co_group(self, other: "DataStream") -> "CoGroupedStreams":
+        """DataStream.coGroup (RS/api/datastream/DataStream.java): a window coGroup with `other`."""
+        return CoGroupedStreams(self, other)
+
+    coGroup = co_group
 
 
 class StreamExecutionEnvironment:

@@ -549,8 +549,38 @@ int  gw_top_n_host(int64_t n, const int64_t* key, const int64_t* start, const in
  * The emitted element's timestamp is end - 1, which gw_encode_rows_* writes: the five columns
  * are the (key, start, end, 8 bytes, payload) columns it takes.
  * Not offered: allowed lateness > 0, PurgingTrigger and evictors, session and count windows
- * (GW_E_UNSUPPORTED at create), coGroup / outer joins, snapshots, key_hash columns, the RCCL
- * exchange (partition the inputs with gw_partition_device), network-buffer ingest.
+ * (GW_E_UNSUPPORTED at create), snapshots, key_hash columns, the RCCL exchange (partition the
+ * inputs with gw_partition_device), network-buffer ingest, null fields in gw_encode_rows_*.
+ *
+ * coGroup and outer joins.  CoGroupedStreams is the primitive under the join: at the fire
+ * CoGroupFunction.coGroup sees every (key, window) with a record on either side, one Iterable
+ * possibly empty, and every outer window join is written as one.  Two forms:
+ * - the outer modes, the closed set of CoGroupFunctions that run wholly on the device.  A fired
+ *   (window, key) group with L left and R right records gives L * R rows when both are positive,
+ *   L rows when R = 0 and the mode has bit 0 (GW_JOIN_MODE_LEFT_OUTER), R rows when L = 0 and the
+ *   mode has bit 1 (GW_JOIN_MODE_RIGHT_OUTER), otherwise none.  An unmatched row carries its own
+ *   side's payload and the caller's null_payload in the lacking side's column, so the five columns
+ *   feed gw_encode_rows_* as they are and the caller chooses its id for null.  The optional sixth
+ *   column `present` (one byte per row; may be NULL) is 1 = left only, 2 = right only, 3 = both,
+ *   whatever the payloads are.  Order as above; a group's unmatched rows in arrival order.
+ *   GW_JOIN_MODE_INNER gives exactly the rows of the inner join, `present` all 3.
+ * - the groups themselves as a CSR: per fired group (key, start, end) and offsets loff, roff (one
+ *   entry more than groups, loff[0] = roff[0] = 0) into two element columns: group g's left
+ *   payloads are lelem[loff[g] .. loff[g + 1]) in arrival order, likewise right.  Groups in the
+ *   order above.
+ *
+ * gw_window_join_outer_device / _host: gw_window_join_device / _host with a mode, null_payload
+ * and d_present_out (cap bytes, or NULL).  A call with one empty side is not empty: with n_l = 0,
+ * right and full outer emit every fired right record, and the other way round; both empty: GW_OK,
+ * no rows.  cap too small: GW_E_OUTPUT_FULL, the needed number in *n_out, nothing written.  More
+ * than INT64_MAX / 41 rows: GW_E_RANGE.  An unknown mode: GW_E_INVALID.  _device_timed: as
+ * gw_window_join_device_timed.
+ * gw_window_cogroup_device / _host: the CSR of the interval's groups.  d_key_out, d_start_out,
+ * d_end_out: cap_groups rows; d_loff_out, d_roff_out: cap_groups + 1 rows (never NULL); the
+ * element columns cap_left and cap_right rows.  n_out: int64[3] = groups, left elements, right
+ * elements.  Any of the three caps too small: GW_E_OUTPUT_FULL, all three needed numbers in n_out,
+ * nothing written.  Limits and errors as the join's.  _device_timed also reports the time of the
+ * two kernels that write the CSR (*write_ms), for measurements.
  *
  * gw_window_join_device: stateless; n_l left and n_r right records in arrival order in device
  * columns, the geometry and the interval (w0, w1]; the pairs of the windows firing in it, in the
@@ -573,10 +603,29 @@ int  gw_top_n_host(int64_t n, const int64_t* key, const int64_t* start, const in
  * and removes them (GW_E_OUTPUT_FULL while pairs remain), gw_join_rows_device is the zero-copy
  * view, gw_join_clear_rows drops them.  After GW_E_NO_TIMESTAMP, GW_E_RANGE or a device error
  * every call returns GW_E_STATE.  max_batch: records per device pass of an ingest (0: 2^22);
- * capacity_hint: initial log rows per side. */
+ * capacity_hint: initial log rows per side.
+ * gw_join_set_mode: an outer mode (with its null_payload) or GW_JOIN_MODE_COGROUP for the handle;
+ * only before the first ingest or watermark (GW_E_STATE afterwards, the handle goes on as it was);
+ * the default is inner.  Late filtering, log growth and log compaction do not depend on the mode.
+ * Outer modes: gw_join_advance_watermark appends the mode's rows and *pairs_fired counts them;
+ * gw_join_drain and gw_join_rows_device give the five columns, gw_join_drain_outer and
+ * gw_join_rows_device_outer add `present` (may be NULL).  coGroup mode: a fire appends its groups
+ * and elements to the pending CSR, the offsets rebased by the pending totals, so several
+ * watermarks accumulate into one valid CSR; *pairs_fired is the number of groups.
+ * gw_join_cogroup_pending: n[3] = pending groups, left and right elements.  gw_join_cogroup_drain
+ * copies everything and removes it, all or nothing: GW_E_OUTPUT_FULL with the needed numbers in
+ * n[3] otherwise (loff, roff: cap_groups + 1 rows).  gw_join_cogroup_rows_device: the zero-copy
+ * view (NULL for an empty column).  gw_join_clear_rows clears either form.  The pair accessors
+ * (gw_join_pending, _drain*, _rows_device*) return GW_E_INVALID on a coGroup handle and the
+ * coGroup accessors on any other. */
 #define GW_JOIN_MAX_WINDOWS 64
 #define GW_JOIN_LEFT  0
 #define GW_JOIN_RIGHT 1
+#define GW_JOIN_MODE_INNER       0
+#define GW_JOIN_MODE_LEFT_OUTER  1   /* bit 0: keep left records without a partner  */
+#define GW_JOIN_MODE_RIGHT_OUTER 2   /* bit 1: keep right records without a partner */
+#define GW_JOIN_MODE_FULL_OUTER  3
+#define GW_JOIN_MODE_COGROUP     4   /* gw_join_set_mode only: the groups as a CSR   */
 int  gw_window_join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
                            int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
                            int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
@@ -591,6 +640,44 @@ int  gw_window_join_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, c
                          const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
                          int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out,
                          int64_t* end_out, int64_t* lpay_out, int64_t* rpay_out, int64_t cap, int64_t* n_out);
+int  gw_window_join_outer_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                 int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                 int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1, int32_t mode,
+                                 int64_t null_payload, int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out,
+                                 int64_t* d_lpay_out, int64_t* d_rpay_out, uint8_t* d_present_out, int64_t cap,
+                                 int64_t* n_out, void* stream);
+int  gw_window_join_outer_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                       int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                       int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+                                       int32_t mode, int64_t null_payload, int64_t* d_key_out, int64_t* d_start_out,
+                                       int64_t* d_end_out, int64_t* d_lpay_out, int64_t* d_rpay_out,
+                                       uint8_t* d_present_out, int64_t cap, int64_t* n_out, void* stream,
+                                       double* expand_ms);
+int  gw_window_join_outer_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                               const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size,
+                               int64_t slide, int64_t offset, int64_t w0, int64_t w1, int32_t mode,
+                               int64_t null_payload, int64_t* key_out, int64_t* start_out, int64_t* end_out,
+                               int64_t* lpay_out, int64_t* rpay_out, uint8_t* present_out, int64_t cap,
+                               int64_t* n_out);
+int  gw_window_cogroup_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                              int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                              int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+                              int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out, int64_t* d_loff_out,
+                              int64_t* d_roff_out, int64_t* d_lelem_out, int64_t cap_left, int64_t* d_relem_out,
+                              int64_t cap_right, int64_t cap_groups, int64_t* n_out, void* stream);
+int  gw_window_cogroup_device_timed(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts, const int64_t* d_lpay,
+                                    int64_t n_r, const int64_t* d_rkey, const int64_t* d_rts, const int64_t* d_rpay,
+                                    int64_t size, int64_t slide, int64_t offset, int64_t w0, int64_t w1,
+                                    int64_t* d_key_out, int64_t* d_start_out, int64_t* d_end_out, int64_t* d_loff_out,
+                                    int64_t* d_roff_out, int64_t* d_lelem_out, int64_t cap_left, int64_t* d_relem_out,
+                                    int64_t cap_right, int64_t cap_groups, int64_t* n_out, void* stream,
+                                    double* write_ms);
+int  gw_window_cogroup_host(int64_t n_l, const int64_t* lkey, const int64_t* lts, const int64_t* lpay, int64_t n_r,
+                            const int64_t* rkey, const int64_t* rts, const int64_t* rpay, int64_t size, int64_t slide,
+                            int64_t offset, int64_t w0, int64_t w1, int64_t* key_out, int64_t* start_out,
+                            int64_t* end_out, int64_t* loff_out, int64_t* roff_out, int64_t* lelem_out,
+                            int64_t cap_left, int64_t* relem_out, int64_t cap_right, int64_t cap_groups,
+                            int64_t* n_out);
 
 typedef struct gw_join gw_join;
 typedef struct gw_join_config {
@@ -625,6 +712,19 @@ int  gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64
 int  gw_join_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
                          const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n);
 int  gw_join_clear_rows(gw_join* h);
+int  gw_join_set_mode(gw_join* h, int32_t mode, int64_t null_payload);
+int  gw_join_drain_outer(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay,
+                         uint8_t* present, int64_t cap, int64_t* n);
+int  gw_join_rows_device_outer(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                               const int64_t** d_lpay, const int64_t** d_rpay, const uint8_t** d_present,
+                               int64_t* n);
+int  gw_join_cogroup_pending(gw_join* h, int64_t* n);
+int  gw_join_cogroup_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* loff, int64_t* roff,
+                           int64_t* lelem, int64_t cap_left, int64_t* relem, int64_t cap_right, int64_t cap_groups,
+                           int64_t* n);
+int  gw_join_cogroup_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
+                                 const int64_t** d_loff, const int64_t** d_roff, const int64_t** d_lelem,
+                                 const int64_t** d_relem, int64_t* n);
 int64_t gw_join_late_dropped(const gw_join* h);
 int  gw_join_get_stats(const gw_join* h, gw_join_stats* out);
 void* gw_join_stream(gw_join* h);
