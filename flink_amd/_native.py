@@ -74,7 +74,12 @@ EXPORTS = [
     "gw_window_cogroup_device", "gw_window_cogroup_device_timed", "gw_window_cogroup_host",
     "gw_join_set_mode", "gw_join_drain_outer", "gw_join_rows_device_outer", "gw_join_cogroup_pending",
     "gw_join_cogroup_drain", "gw_join_cogroup_rows_device",
+    "gw_interval_join_device", "gw_interval_join_device_timed", "gw_interval_join_host",
+    "gw_ijoin_create", "gw_ijoin_destroy", "gw_ijoin_last_error", "gw_ijoin_ingest", "gw_ijoin_ingest_device",
+    "gw_ijoin_advance_watermark", "gw_ijoin_end_input", "gw_ijoin_pending", "gw_ijoin_drain", "gw_ijoin_rows_device",
+    "gw_ijoin_clear_rows", "gw_ijoin_late_dropped", "gw_ijoin_get_stats", "gw_ijoin_last_times", "gw_ijoin_stream",
 ]
+IJOIN_MAX_BOUND = 1 << 62  # gpuwin.h GW_IJOIN_MAX_BOUND
 JOIN_MAX_WINDOWS = 64  # gpuwin.h GW_JOIN_MAX_WINDOWS
 JOIN_LEFT, JOIN_RIGHT = 0, 1
 # gpuwin.h GW_JOIN_MODE_*: bit 0 keeps unmatched left records, bit 1 unmatched right records
@@ -196,6 +201,22 @@ class GwJoinStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in (
         "live_left", "live_right", "log_capacity_left", "log_capacity_right", "fires", "pairs_fired",
         "log_growths", "last_fire_tuples")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GwIJoinConfig(ctypes.Structure):
+    _fields_ = [
+        ("lower", ctypes.c_int64), ("upper", ctypes.c_int64), ("device", ctypes.c_int32),
+        ("capacity_hint", ctypes.c_int64), ("max_batch", ctypes.c_int64),
+    ]
+
+
+class GwIJoinStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "live_left", "live_right", "log_capacity_left", "log_capacity_right", "rows_emitted", "log_growths",
+        "merges", "last_call_rows")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -364,6 +385,26 @@ def lib() -> ctypes.CDLL:
         "gw_join_cogroup_pending": (c_int, [p, P64]),
         "gw_join_cogroup_drain": (c_int, [p, p, p, p, p, p, p, i64, p, i64, i64, P64]),
         "gw_join_cogroup_rows_device": (c_int, [p] + [ctypes.POINTER(p)] * 7 + [P64]),
+        "gw_interval_join_device": (c_int, [i32, i64, p, p, p, i64, p, p, p, i64, i64, p, p, p, p, p, i64, P64, p]),
+        "gw_interval_join_device_timed": (c_int, [i32, i64, p, p, p, i64, p, p, p, i64, i64, p, p, p, p, p, i64, P64, p,
+                                                  ctypes.POINTER(ctypes.c_double)]),
+        "gw_interval_join_host": (c_int, [i32, i64, p, p, p, i64, p, p, p, i64, i64, p, p, p, p, p, i64, P64]),
+        "gw_ijoin_create": (c_int, [ctypes.POINTER(GwIJoinConfig), ctypes.POINTER(p)]),
+        "gw_ijoin_destroy": (c_int, [p]),
+        "gw_ijoin_last_error": (ctypes.c_char_p, [p]),
+        "gw_ijoin_ingest": (c_int, [p, i32, i64, p, p, p, P64]),
+        "gw_ijoin_ingest_device": (c_int, [p, i32, i64, p, p, p, p, P64]),
+        "gw_ijoin_advance_watermark": (c_int, [p, i64]),
+        "gw_ijoin_end_input": (c_int, [p]),
+        "gw_ijoin_pending": (c_int, [p, P64]),
+        "gw_ijoin_drain": (c_int, [p, p, p, p, p, p, i64, P64]),
+        "gw_ijoin_rows_device": (c_int, [p, ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p),
+                                         ctypes.POINTER(p), P64]),
+        "gw_ijoin_clear_rows": (c_int, [p]),
+        "gw_ijoin_late_dropped": (i64, [p]),
+        "gw_ijoin_get_stats": (c_int, [p, ctypes.POINTER(GwIJoinStats)]),
+        "gw_ijoin_last_times": (c_int, [p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+        "gw_ijoin_stream": (p, [p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

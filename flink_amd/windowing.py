@@ -510,6 +510,54 @@ def window_cogroup_host(lkey, lts, lpay, rkey, rts, rpay, assigner: WindowAssign
     return (g[0][:n[0]], g[1][:n[0]], g[2][:n[0]], g[3][:n[0] + 1], g[4][:n[0] + 1], le[:n[1]], re[:n[2]])
 
 
+def interval_join_device(probe_side: int, pkey, pts, ppay, bkey, bts, bpay, lower: int, upper: int, stream=None):
+    """gw_interval_join_device over torch device tensors (int64): the rows of one ingest call of
+    `probe_side` (0 left, 1 right) against a buffer of the other side's records in arrival order.
+    A left l and a right r pair when l.key == r.key and l.ts + lower <= r.ts <= l.ts + upper (both
+    inclusive, relative to the left record whichever side probes).  Returns device tensors (key,
+    left ts, right ts, left payload, right payload): the probes in arrival order, each one's
+    partners by ascending (ts, arrival).  No late filtering.  Waits on `stream` (default: torch's
+    current)."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(pkey.device).cuda_stream
+    n_out = ctypes.c_int64(0)
+    cap = max(pkey.numel(), bkey.numel(), 1)
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    while True:
+        out = [torch.empty(cap, dtype=torch.int64, device=pkey.device) for _ in range(5)]
+        rc = N.lib().gw_interval_join_device(int(probe_side), pkey.numel(), P(pkey), P(pts), P(ppay), bkey.numel(), P(bkey),
+                                             P(bts), P(bpay), int(lower), int(upper), *[o.data_ptr() for o in out], cap,
+                                             ctypes.byref(n_out), ctypes.c_void_p(stream) if stream else None)
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    return tuple(o[:n_out.value] for o in out)
+
+
+def interval_join_host(probe_side: int, pkey, pts, ppay, bkey, bts, bpay, lower: int, upper: int):
+    """gw_interval_join_host over numpy columns: the contract of interval_join_device as plain
+    host code (no device)."""
+    cols = [np.ascontiguousarray(x, dtype=np.int64) for x in (pkey, pts, ppay, bkey, bts, bpay)]
+    if not (len(cols[0]) == len(cols[1]) == len(cols[2]) and len(cols[3]) == len(cols[4]) == len(cols[5])):
+        raise ValueError("column lengths differ")
+    n_out = ctypes.c_int64(0)
+    cap = max(len(cols[0]), len(cols[3]), 1)
+    while True:
+        out = [np.empty(cap, np.int64) for _ in range(5)]
+        rc = N.lib().gw_interval_join_host(int(probe_side), len(cols[0]), *[_ptr(c) for c in cols[:3]], len(cols[3]),
+                                           *[_ptr(c) for c in cols[3:]], int(lower), int(upper), *[_ptr(o) for o in out],
+                                           cap, ctypes.byref(n_out))
+        if rc == N.GW_E_OUTPUT_FULL and n_out.value > cap:
+            cap = n_out.value
+            continue
+        N.check(rc)
+        break
+    return tuple(o[:n_out.value] for o in out)
+
+
 # ------------------------------------------------------------------------ operator
 class StatusWatermarkValve:
     """The valve of an input gate with n channels (gw_valve; host code, no device): feed it each
@@ -1592,6 +1640,252 @@ class CoGroupedStreams(JoinedStreams):
         return out
 
 
+class GpuIntervalJoinOperator:
+    """Event-time interval join of two keyed streams on one MI355X (gw_ijoin): Flink's
+    keyedA.intervalJoin(keyedB).between(lower, upper).process(), i.e. IntervalJoinOperator.  A left
+    l and a right r pair when l.key == r.key and l.ts + lower <= r.ts <= l.ts + upper (inclusive).
+    Records are (key, ts, payload) int64 columns per side; process_batch joins a batch against the
+    other side's buffer as it stands and returns the number of rows it made: (key, left ts, right
+    ts, left payload, right payload), the batch's records in arrival order, each one's partners by
+    ascending (ts, arrival).  A watermark emits nothing; it drops the late records of later
+    batches and removes the buffered records whose cleanup time has passed."""
+
+    LEFT, RIGHT = N.JOIN_LEFT, N.JOIN_RIGHT
+
+    def __init__(self, lower: int, upper: int, device: int = 0, capacity_hint: int = 0, max_batch: int = 0):
+        lower, upper = int(lower), int(upper)
+        if lower > upper:
+            raise ValueError("interval join: lower bound must not be greater than the upper bound")
+        if lower < -N.IJOIN_MAX_BOUND or upper > N.IJOIN_MAX_BOUND:
+            raise ValueError("interval join: bounds beyond +-2^62")
+        c = N.GwIJoinConfig()
+        c.lower, c.upper, c.device, c.capacity_hint, c.max_batch = lower, upper, device, capacity_hint, max_batch
+        self.lower, self.upper = lower, upper
+        self.cfg = c
+        self._h = None
+
+    def open(self):
+        h = ctypes.c_void_p()
+        rc = N.lib().gw_ijoin_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc == N.GW_E_INVALID:
+            raise ValueError(N.lib().gw_last_error(None).decode())
+        N.check(rc, None)
+        self._h = h
+        return self
+
+    def close(self):
+        if self._h:
+            N.lib().gw_ijoin_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self.open() if self._h is None else self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc != N.GW_OK:
+            msg = N.lib().gw_ijoin_last_error(self._h)
+            raise N.GpuWinError(rc, msg.decode() if msg else "")
+        return rc
+
+    def process_batch(self, side: int, keys, ts, payload) -> int:
+        keys, ts, payload = (np.ascontiguousarray(x, dtype=np.int64) for x in (keys, ts, payload))
+        if not (len(keys) == len(ts) == len(payload)):
+            raise ValueError("column lengths differ")
+        rows = ctypes.c_int64(0)
+        self._check(N.lib().gw_ijoin_ingest(self._h, int(side), len(keys), _ptr(keys), _ptr(ts), _ptr(payload),
+                                            ctypes.byref(rows)))
+        return rows.value
+
+    def process_batch_device(self, side: int, keys, ts, payload, stream=None) -> int:
+        """Columns already in HBM (torch int64 tensors), produced on `stream` (default: torch's
+        current): the operator reads them behind that stream's work, and the stream waits for
+        the reads."""
+        if not (keys.numel() == ts.numel() == payload.numel()):
+            raise ValueError("column lengths differ")
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(keys.device).cuda_stream
+        P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+        rows = ctypes.c_int64(0)
+        self._check(N.lib().gw_ijoin_ingest_device(self._h, int(side), keys.numel(), P(keys), P(ts), P(payload),
+                                                   ctypes.c_void_p(stream) if stream else None, ctypes.byref(rows)))
+        return rows.value
+
+    def advance_watermark(self, wm: int):
+        self._check(N.lib().gw_ijoin_advance_watermark(self._h, int(wm)))
+
+    def end_input(self):
+        self._check(N.lib().gw_ijoin_end_input(self._h))
+
+    def pending(self) -> int:
+        n = ctypes.c_int64(0)
+        self._check(N.lib().gw_ijoin_pending(self._h, ctypes.byref(n)))
+        return n.value
+
+    def drain(self, cap: Optional[int] = None):
+        """All pending rows as numpy (key, left ts, right ts, left payload, right payload), copied
+        cap rows per call (default: all at once)."""
+        n = self.pending()
+        out = [np.empty(n, np.int64) for _ in range(5)]
+        step = n if cap is None else max(1, int(cap))
+        at = 0
+        got = ctypes.c_int64(0)
+        while at < n:
+            rc = N.lib().gw_ijoin_drain(self._h, *[ctypes.c_void_p(o.ctypes.data + 8 * at) for o in out], step,
+                                        ctypes.byref(got))
+            if rc != N.GW_E_OUTPUT_FULL:
+                self._check(rc)
+            at += got.value
+            if rc == N.GW_OK:
+                break
+        assert at == n
+        return tuple(out)
+
+    def rows_device(self):
+        """Zero-copy view of the pending rows: five device pointers and their number."""
+        p = [ctypes.c_void_p() for _ in range(5)]
+        n = ctypes.c_int64(0)
+        self._check(N.lib().gw_ijoin_rows_device(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
+        return [x.value for x in p], n.value
+
+    def clear_rows(self):
+        self._check(N.lib().gw_ijoin_clear_rows(self._h))
+
+    def num_late_records_dropped(self) -> int:
+        return int(N.lib().gw_ijoin_late_dropped(self._h))
+
+    def stats(self) -> dict:
+        s = N.GwIJoinStats()
+        N.lib().gw_ijoin_get_stats(self._h, ctypes.byref(s))
+        return s.as_dict()
+
+    def last_times(self):
+        """(probe stage ms, merge ms) of the last ingest pass on the device; waits for the stream."""
+        a, b = ctypes.c_double(0), ctypes.c_double(0)
+        self._check(N.lib().gw_ijoin_last_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    @property
+    def stream(self) -> int:
+        return N.lib().gw_ijoin_stream(self._h) or 0
+
+
+@dataclass
+class IntervalJoinContext:
+    """ProcessJoinFunction.Context: the two records' timestamps and the result's (their maximum)."""
+    left_timestamp: int
+    right_timestamp: int
+    timestamp: int
+
+
+class IntervalJoined:
+    """keyedA.interval_join(keyedB) -- KeyedStream.IntervalJoin / IntervalJoined
+    (RS/api/datastream/KeyedStream.java): between(lower, upper)[.lower_bound_exclusive()]
+    [.upper_bound_exclusive()].process(fn).execute_and_collect()."""
+
+    def __init__(self, left: "KeyedStream", right: "KeyedStream"):
+        self.left, self.right = left, right
+        self.lower = self.upper = None
+        self._fn = None
+
+    def between(self, lower, upper) -> "IntervalJoined":
+        lower, upper = int(lower), int(upper)
+        if lower > upper:
+            raise ValueError("between(): lower bound must not be greater than the upper bound")
+        self.lower, self.upper = lower, upper
+        return self
+
+    def _bounds_set(self):
+        if self.lower is None:
+            raise ValueError("between() first")
+
+    def lower_bound_exclusive(self) -> "IntervalJoined":
+        """IntervalJoined.lowerBoundExclusive: the lower bound plus one (checked afterwards)."""
+        self._bounds_set()
+        if self.lower + 1 > self.upper:
+            raise ValueError("lower_bound_exclusive(): the interval would be empty")
+        self.lower += 1
+        return self
+
+    def upper_bound_exclusive(self) -> "IntervalJoined":
+        """IntervalJoined.upperBoundExclusive: the upper bound minus one (checked afterwards)."""
+        self._bounds_set()
+        if self.lower > self.upper - 1:
+            raise ValueError("upper_bound_exclusive(): the interval would be empty")
+        self.upper -= 1
+        return self
+
+    lowerBoundExclusive, upperBoundExclusive = lower_bound_exclusive, upper_bound_exclusive
+
+    def process(self, process_join_function: Callable) -> "IntervalJoined":
+        self._bounds_set()
+        self._fn = process_join_function
+        return self
+
+    def execute_and_collect(self) -> list:
+        """Both bounded sources through one interval join operator.  Unlike a window join, here
+        the interleaving of the two inputs decides the result (a record meets only what the other
+        side's buffer holds when it arrives, and a watermark cleans buffers and makes later
+        records late), so the schedule is fixed: the sources are consumed in turn, the left up to
+        and including its next Watermark, then the right up to its next, and so on; a source that
+        has run out is skipped.  The records of one turn are one ingest call.  The operator's
+        watermark is the minimum of the two inputs' last watermarks (Long.MIN_VALUE before an
+        input's first), a finished source counting as Long.MAX_VALUE.  Returns fn(left, right,
+        ctx) per pair as StreamRecords stamped max(left ts, right ts), turns in order, within a
+        turn the operator's order."""
+        if self._fn is None:
+            raise ValueError("process() before execute_and_collect()")
+        sides = (self.left, self.right)
+        elems = [list(s.elements) for s in sides]
+        recs = [[e for e in el if isinstance(e, StreamRecord)] for el in elems]
+        keys_in = {}
+        allk = [sides[sd].key_selector(e.value) for sd in (0, 1) for e in recs[sd]]
+        int_keys = all(isinstance(k, int) and not isinstance(k, bool) and LONG_MIN <= k <= LONG_MAX for k in allk)
+        enc = (lambda k: k) if int_keys else (lambda k: keys_in.setdefault(k, len(keys_in)))
+        kw = {k: v for k, v in self.left.env.op_kwargs.items() if k in ("device", "capacity_hint", "max_batch")}
+        out = []
+        with GpuIntervalJoinOperator(self.lower, self.upper, **kw) as op:
+            at, seen = [0, 0], [0, 0]
+            wm_in = [LONG_MIN if el else LONG_MAX for el in elems]
+            side = 0
+            while at[0] < len(elems[0]) or at[1] < len(elems[1]):
+                if at[side] < len(elems[side]):
+                    batch, mark = [], None
+                    while at[side] < len(elems[side]) and mark is None:
+                        e = elems[side][at[side]]
+                        at[side] += 1
+                        if isinstance(e, Watermark):
+                            mark = e.timestamp
+                        else:
+                            batch.append(e)
+                    if batch:
+                        sel = sides[side].key_selector
+                        op.process_batch(side, [enc(sel(e.value)) for e in batch], [int(e.timestamp) for e in batch],
+                                         list(range(seen[side], seen[side] + len(batch))))
+                        seen[side] += len(batch)
+                        _, lt, rt, lp, rp = op.drain()
+                        for i in range(len(lt)):
+                            ts = max(int(lt[i]), int(rt[i]))
+                            ctx = IntervalJoinContext(int(lt[i]), int(rt[i]), ts)
+                            out.append(StreamRecord(self._fn(recs[0][int(lp[i])].value, recs[1][int(rp[i])].value, ctx), ts))
+                    if mark is not None:
+                        wm_in[side] = max(wm_in[side], int(mark))
+                    if at[side] >= len(elems[side]):
+                        wm_in[side] = LONG_MAX
+                    op.advance_watermark(min(wm_in))
+                side = 1 - side
+        return out
+
+
 class WindowedStream:
     """keyBy(...).window(assigner) — WindowedStream (RS/api/datastream/WindowedStream.java:84-96)."""
 
@@ -1727,8 +2021,16 @@ class WindowAllTopN:
 
 
 class KeyedStream:
-    def __init__(self, env, key_selector):
+    def __init__(self, env, key_selector, elements=None):
         self.env, self.key_selector = env, key_selector
+        self.elements = env.elements if elements is None else elements  # this stream's own source
+
+    def interval_join(self, other: "KeyedStream") -> IntervalJoined:
+        """KeyedStream.intervalJoin (RS/api/datastream/KeyedStream.java): this stream is the left
+        side, `other` the right."""
+        return IntervalJoined(self, other)
+
+    intervalJoin = interval_join
 
     def window(self, assigner: WindowAssigner) -> WindowedStream:
         return WindowedStream(self, assigner)
@@ -1746,7 +2048,7 @@ class DataStream:
         self.elements = env.elements if elements is None else elements  # this stream's own source
 
     def key_by(self, key_selector) -> KeyedStream:
-        return KeyedStream(self.env, key_selector)
+        return KeyedStream(self.env, key_selector, self.elements)
 
     keyBy = key_by
 

@@ -729,6 +729,113 @@ int64_t gw_join_late_dropped(const gw_join* h);
 int  gw_join_get_stats(const gw_join* h, gw_join_stats* out);
 void* gw_join_stream(gw_join* h);
 
+/* ---- event-time interval join of two keyed streams -------------------------------
+ * keyedA.intervalJoin(keyedB).between(lower, upper).process(ProcessJoinFunction): KeyedStream
+ * .IntervalJoined on IntervalJoinOperator (RS/api/operators/co/IntervalJoinOperator.java), not
+ * WindowOperator.  Records are (key, ts, payload) int64 columns per side (GW_JOIN_LEFT /
+ * GW_JOIN_RIGHT).  A left l and a right r match when
+ *     l.key == r.key  and  l.ts + lower <= r.ts <= l.ts + upper,
+ * lower <= upper both inclusive and always relative to the left record (lowerBoundExclusive /
+ * upperBoundExclusive are lower + 1 / upper - 1, the caller's arithmetic).  A row is
+ * (key, left ts, right ts, left payload, right payload); the element's timestamp is
+ * max(left ts, right ts), which the caller derives.
+ *
+ * One ingest call of side S with n records at the handle's watermark w is n processElementS
+ * calls in order: any ts == Long.MIN_VALUE in the call is GW_E_NO_TIMESTAMP (checked over the
+ * whole call, before the late test); record i is late when w != Long.MIN_VALUE and ts[i] < w,
+ * and is dropped and counted; for every other record ts + lower and ts + upper (left) or
+ * ts - upper and ts - lower (right) must fit int64, else GW_E_RANGE (Java wraps silently; this
+ * fails instead, as the window join does).  On either error nothing of the call is appended or
+ * emitted and every later call on the handle returns GW_E_STATE.  Each record that is not late is
+ * appended to its side's buffer and joined against the other side's buffer as it stands: records
+ * of one call never pair with each other.  Order of a call's rows: its records in arrival order;
+ * within one record its partners by ascending (partner ts, partner arrival), arrival being
+ * (ingest call, index).  Flink's inner order is a HashMap's; this is one of its valid orders.  A
+ * call longer than max_batch runs in passes and gives the same rows in the same order.
+ *
+ * A watermark greater than the current one emits nothing and removes the buffered records whose
+ * cleanup time is <= it: left ts + upper if upper > 0 else ts; right ts - lower if lower < 0 else
+ * ts (onEventTime's two namespaces).  A watermark that does not advance is ignored; the end of
+ * input is Long.MAX_VALUE.  So a pair inside the bounds is not emitted when the earlier record
+ * was cleaned at exactly the watermark the later one arrives on (ts == w is not late).
+ *
+ * gw_interval_join_device: stateless; the rows of one ingest call of probe_side (n_p records
+ * in device columns) against a buffer of n_b records of the other side given in arrival order.
+ * No late filtering; the Long.MIN_VALUE and range checks cover both sides.  cap too small:
+ * GW_E_OUTPUT_FULL with the needed number in *n_out and nothing written.  Either side empty:
+ * GW_OK and no rows (the other side is not read).  lower > upper or a bound beyond +-2^62:
+ * GW_E_INVALID; more than 2^30 - 1 records on a side: GW_E_UNSUPPORTED; more than INT64_MAX / 40
+ * rows: GW_E_RANGE.  Waits on `stream`; its scratch is per device and grows as needed.
+ * gw_interval_join_device_timed also reports the time of its expand kernel between two HIP
+ * events.  gw_interval_join_host: the same contract as plain host code over host arrays.
+ *
+ * gw_ijoin: the operator.  Each side's records live in a device log kept sorted by (key, ts),
+ * equal (key, ts) in arrival order; an ingest sorts its batch, probes the other side's log,
+ * expands the rows and merges the batch into its own log (*rows: the rows of this call, may be
+ * NULL).  gw_ijoin_ingest_device orders itself with `stream` as gw_join_ingest_device does.  Rows
+ * of several calls accumulate until drained or cleared: gw_ijoin_drain copies up to cap and
+ * removes them (GW_E_OUTPUT_FULL while rows remain), gw_ijoin_rows_device is the zero-copy view
+ * (it waits for the handle's stream, so the rows it shows are written), gw_ijoin_clear_rows
+ * drops them.  gw_ijoin_last_times: the device time of the last ingest
+ * pass's probe stage (probe, scans, descriptors) and of its merge, in milliseconds; it waits for
+ * the handle's stream.
+ *
+ * Not offered: the late side outputs (sideOutputLeftLateData / Right), snapshots, key_hash
+ * columns, the RCCL exchange, network-buffer ingest, and gw_encode_rows_* of these rows (the
+ * encoder stamps end - 1, not max(left ts, right ts)). */
+#define GW_IJOIN_MAX_BOUND ((int64_t)1 << 62)
+int  gw_interval_join_device(int32_t probe_side, int64_t n_p, const int64_t* d_pkey, const int64_t* d_pts,
+                             const int64_t* d_ppay, int64_t n_b, const int64_t* d_bkey, const int64_t* d_bts,
+                             const int64_t* d_bpay, int64_t lower, int64_t upper, int64_t* d_key_out,
+                             int64_t* d_lts_out, int64_t* d_rts_out, int64_t* d_lpay_out, int64_t* d_rpay_out,
+                             int64_t cap, int64_t* n_out, void* stream);
+int  gw_interval_join_device_timed(int32_t probe_side, int64_t n_p, const int64_t* d_pkey, const int64_t* d_pts,
+                                   const int64_t* d_ppay, int64_t n_b, const int64_t* d_bkey, const int64_t* d_bts,
+                                   const int64_t* d_bpay, int64_t lower, int64_t upper, int64_t* d_key_out,
+                                   int64_t* d_lts_out, int64_t* d_rts_out, int64_t* d_lpay_out,
+                                   int64_t* d_rpay_out, int64_t cap, int64_t* n_out, void* stream,
+                                   double* expand_ms);
+int  gw_interval_join_host(int32_t probe_side, int64_t n_p, const int64_t* pkey, const int64_t* pts,
+                           const int64_t* ppay, int64_t n_b, const int64_t* bkey, const int64_t* bts,
+                           const int64_t* bpay, int64_t lower, int64_t upper, int64_t* key_out, int64_t* lts_out,
+                           int64_t* rts_out, int64_t* lpay_out, int64_t* rpay_out, int64_t cap, int64_t* n_out);
+
+typedef struct gw_ijoin gw_ijoin;
+typedef struct gw_ijoin_config {
+    int64_t lower;           /* inclusive, relative to the left record            */
+    int64_t upper;
+    int32_t device;
+    int64_t capacity_hint;   /* initial rows of each side's log (0: 16)           */
+    int64_t max_batch;       /* records per device pass of an ingest (0: 2^22)    */
+} gw_ijoin_config;
+typedef struct gw_ijoin_stats {
+    int64_t live_left, live_right;                  /* records in the logs        */
+    int64_t log_capacity_left, log_capacity_right;  /* rows allocated             */
+    int64_t rows_emitted;
+    int64_t log_growths;
+    int64_t merges;                                 /* ingest passes that merged  */
+    int64_t last_call_rows;                         /* rows of the last ingest    */
+} gw_ijoin_stats;
+int  gw_ijoin_create(const gw_ijoin_config* cfg, gw_ijoin** out);
+int  gw_ijoin_destroy(gw_ijoin* h);
+const char* gw_ijoin_last_error(const gw_ijoin* h);
+int  gw_ijoin_ingest(gw_ijoin* h, int32_t side, int64_t n, const int64_t* key, const int64_t* ts,
+                     const int64_t* payload, int64_t* rows);
+int  gw_ijoin_ingest_device(gw_ijoin* h, int32_t side, int64_t n, const int64_t* d_key, const int64_t* d_ts,
+                            const int64_t* d_payload, void* stream, int64_t* rows);
+int  gw_ijoin_advance_watermark(gw_ijoin* h, int64_t watermark);
+int  gw_ijoin_end_input(gw_ijoin* h);
+int  gw_ijoin_pending(gw_ijoin* h, int64_t* n);
+int  gw_ijoin_drain(gw_ijoin* h, int64_t* key, int64_t* lts, int64_t* rts, int64_t* lpay, int64_t* rpay,
+                    int64_t cap, int64_t* n);
+int  gw_ijoin_rows_device(gw_ijoin* h, const int64_t** d_key, const int64_t** d_lts, const int64_t** d_rts,
+                          const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n);
+int  gw_ijoin_clear_rows(gw_ijoin* h);
+int64_t gw_ijoin_late_dropped(const gw_ijoin* h);
+int  gw_ijoin_get_stats(const gw_ijoin* h, gw_ijoin_stats* out);
+int  gw_ijoin_last_times(gw_ijoin* h, double* probe_ms, double* merge_ms);
+void* gw_ijoin_stream(gw_ijoin* h);
+
 /* ---- network-buffer output: fired rows as serialized stream elements -------------
  * The output side's counterpart of gw_ingest_serialized*: instead of columns that the JVM turns
  * into one object per row and pushes through TimestampedCollector.collect and
