@@ -37,8 +37,6 @@
 // twice per pass: the kept count with the extremes (it sizes the sort) and the row count with the
 // descriptor count (it sizes the output).
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -46,13 +44,14 @@
 #include <string>
 #include <vector>
 
-#include "gw_devmem.h"
-#include "gw_joinutil.h"
+#include "gw_joinop.h"    // the host side of the operator: OpError, OpStream, RowBuf, staged_ingest (and gw_devmem.h)
+#include "gw_joinutil.h"  // scan_excl, the wave reductions and search, k_compact3, Scratch, Carve
 #include "gw_kernels.h"
 #include "gw_sort.h"
 
 namespace gw {
 
+constexpr const char* kIjName = "interval join";  // the prefix of the shared helpers' messages
 struct IjBounds {
     int64_t lower, upper;  // inclusive, relative to the left record
 };
@@ -155,20 +154,6 @@ __global__ void __launch_bounds__(kJoinThreads) k_ij_evict_flags(int64_t n, cons
     for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads)
         keep[i] = ij_cleanup(side, ts[i], b) > w;
 }
-struct IjCols {
-    const int64_t* in[3];
-    int64_t* out[3];
-};
-__global__ void __launch_bounds__(kJoinThreads) k_ij_compact3(int64_t n, const uint32_t* __restrict__ keep,
-                                                              const uint32_t* __restrict__ off, IjCols c) {
-    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads) {
-        if (!keep[i]) continue;
-        const uint32_t d = off[i];
-        c.out[0][d] = c.in[0][i];
-        c.out[1][d] = c.in[1][i];
-        c.out[2][d] = c.in[2][i];
-    }
-}
 
 // ---- sort -----------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kJoinThreads) k_ij_ts_words(int64_t n, const int64_t* __restrict__ ts, uint64_t min_tw,
@@ -181,7 +166,7 @@ __global__ void __launch_bounds__(kJoinThreads) k_ij_key_words(int64_t n, const 
     for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads)
         w[i] = join_key_word(key[perm[i]]) - min_kw;
 }
-__global__ void __launch_bounds__(kJoinThreads) k_ij_gather3(int64_t n, const uint32_t* __restrict__ perm, IjCols c) {
+__global__ void __launch_bounds__(kJoinThreads) k_ij_gather3(int64_t n, const uint32_t* __restrict__ perm, Cols3 c) {
     for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads) {
         const uint32_t j = perm[i];
         c.out[0][i] = c.in[0][j];
@@ -393,8 +378,8 @@ static hipError_t ij_launch_filter(int64_t n, const int64_t* key, const int64_t*
     hipLaunchKernelGGL(k_ij_filter, dim3(grid_for(n)), dim3(kJoinThreads), 0, s, n, key, ts, side, b, wm, A.keep, A.hdr);
     hipError_t e = scan_excl<uint32_t, uint32_t>(A.keep, A.koff, n, A.blk, A.hdr + IH_KEPT, s);
     if (e != hipSuccess) return e;
-    IjCols c{{key, ts, pay}, {dst[0], dst[1], dst[2]}};
-    hipLaunchKernelGGL(k_ij_compact3, dim3(grid_for(n)), dim3(kJoinThreads), 0, s, n, A.keep, A.koff, c);
+    Cols3 c{{key, ts, pay}, {dst[0], dst[1], dst[2]}};
+    hipLaunchKernelGGL(k_compact3, dim3(grid_for(n)), dim3(kJoinThreads), 0, s, n, A.keep, A.koff, c);
     return hipGetLastError();
 }
 static int ij_flag_error(uint64_t flags, std::string& why) {
@@ -423,7 +408,7 @@ static hipError_t ij_sort(IjArrays& A, int64_t n, const int64_t* h, hipStream_t 
         if (alt) perm = other;
     }
     A.perm = perm;
-    IjCols c{{A.c[0], A.c[1], A.c[2]}, {A.s[0], A.s[1], A.s[2]}};
+    Cols3 c{{A.c[0], A.c[1], A.c[2]}, {A.s[0], A.s[1], A.s[2]}};
     hipLaunchKernelGGL(k_ij_gather3, dim3(g), dim3(kJoinThreads), 0, s, n, perm, c);
     return hipGetLastError();
 }
@@ -442,12 +427,7 @@ static hipError_t ij_launch_probe(IjArrays& A, int64_t n, int side, IjBounds b, 
 }
 static hipError_t ij_launch_expand(const IjArrays& A, int64_t P, int64_t nc, int side, const IjLog& other, const IjOut& out,
                                    hipStream_t s) {
-    // two rows per 16-byte store need the five columns at one alignment
-    int par[5];
-    for (int c = 0; c < 5; ++c) par[c] = (int)(((uintptr_t)out.col[c] >> 3) & 1);
-    const bool vec = par[0] == par[1] && par[0] == par[2] && par[0] == par[3] && par[0] == par[4] &&
-                     !((uintptr_t)out.col[0] & 7);
-    const int shift = vec ? par[0] : 0;
+    const auto [vec, shift] = expand_alignment(out.col);
     const unsigned nblk = (unsigned)((P + shift + kIjTile - 1) / kIjTile);
     const bool left = side == GW_JOIN_LEFT;
 #define IJ_EXPAND(V, L)                                                                                             \
@@ -489,11 +469,6 @@ int ij_args(int32_t probe_side, int64_t n_p, int64_t n_b, int64_t lower, int64_t
     return GW_OK;
 }
 
-int ij_dev_fail(hipError_t e, std::string& why) {
-    why = std::string("interval join: ") + hipGetErrorString(e);
-    return GW_E_DEVICE;
-}
-
 int ij_device(int32_t probe_side, int64_t n_p, const int64_t* d_pkey, const int64_t* d_pts, const int64_t* d_ppay, int64_t n_b,
               const int64_t* d_bkey, const int64_t* d_bts, const int64_t* d_bpay, int64_t lower, int64_t upper,
               int64_t* const* d_out, int64_t cap, int64_t* n_out, hipStream_t s, double* expand_ms, std::string& why) {
@@ -512,51 +487,39 @@ int ij_device(int32_t probe_side, int64_t n_p, const int64_t* d_pkey, const int6
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { why = "interval join: no device"; return GW_E_DEVICE; }
     IjArrays B, A;  // the build side and the probe side
-    Carve size{nullptr};
-    B.carve(size, n_b, false);
-    A.carve(size, n_p, true);
-    if ((rc = scratch_ensure(g_ij_scr[dev], size.at, why))) return rc;
-    Carve cv{g_ij_scr[dev].p};
-    B.carve(cv, n_b, false);
-    A.carve(cv, n_p, true);
+    auto carve = [&](Carve& c) {
+        B.carve(c, n_b, false);
+        A.carve(c, n_p, true);
+    };
+    if ((rc = carve_from(carve, g_ij_scr[dev], kIjName, why))) return rc;
     // no late test (the watermark is Long.MIN_VALUE): the filter is the two checks
     int64_t hb[kIjHdr], hp[kIjHdr];
     hipError_t e = ij_launch_filter(n_b, d_bkey, d_bts, d_bpay, 1 - probe_side, b, INT64_MIN, B, B.c, s);
     if (e == hipSuccess) e = ij_launch_filter(n_p, d_pkey, d_pts, d_ppay, probe_side, b, INT64_MIN, A, A.c, s);
     if (e == hipSuccess) e = hipMemcpyAsync(hb, B.hdr, sizeof hb, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hp, A.hdr, sizeof hp, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return ij_dev_fail(e, why);
+    if (e == hipSuccess) e = read_hdr(hp, A.hdr, kIjHdr, s);
+    if (e != hipSuccess) return dev_fail(kIjName, e, why);
     if ((rc = ij_flag_error((uint64_t)(hb[IH_FLAGS] | hp[IH_FLAGS]), why))) return rc;
-    if ((e = ij_sort(B, n_b, hb, s)) != hipSuccess || (e = ij_sort(A, n_p, hp, s)) != hipSuccess) return ij_dev_fail(e, why);
+    if ((e = ij_sort(B, n_b, hb, s)) != hipSuccess || (e = ij_sort(A, n_p, hp, s)) != hipSuccess) return dev_fail(kIjName, e, why);
     const IjLog build = B.sorted(n_b);
     e = ij_launch_probe(A, n_p, probe_side, b, build, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hp, A.hdr, sizeof hp, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return ij_dev_fail(e, why);
+    if (e == hipSuccess) e = read_hdr(hp, A.hdr, kIjHdr, s);
+    if (e != hipSuccess) return dev_fail(kIjName, e, why);
     const int64_t P = hp[IH_P], nc = hp[IH_NC];
     if (P > kIjMaxRows) { why = "interval join: the rows of one call exceed int64 bytes"; return GW_E_RANGE; }
     *n_out = P;
     if (P > cap) { why = "interval join: output arrays too small"; return GW_E_OUTPUT_FULL; }
     if (P == 0) return GW_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (expand_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) {
-        if (e0) (void)hipEventDestroy(e0);
-        why = "interval join: hipEventCreate";
-        return GW_E_DEVICE;
-    }
+    TimedPair t;
+    if (expand_ms && t.create() != hipSuccess) { why = "interval join: hipEventCreate"; return GW_E_DEVICE; }
     const IjOut out{{d_out[0], d_out[1], d_out[2], d_out[3], d_out[4]}};
-    if (expand_ms) (void)hipEventRecord(e0, s);
+    t.begin(s);
     e = ij_launch_expand(A, P, nc, probe_side, build, out, s);
-    if (expand_ms) (void)hipEventRecord(e1, s);
+    t.end(s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // the scratch is free for the next call
-    if (expand_ms) {
-        float ms = 0;
-        if (e == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *expand_ms = ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    if (e != hipSuccess) return ij_dev_fail(e, why);
+    if (e != hipSuccess) return dev_fail(kIjName, e, why);
+    float ms = 0;
+    if (expand_ms && t.elapsed(&ms) == hipSuccess) *expand_ms = ms;
     return GW_OK;
 }
 
@@ -566,60 +529,25 @@ int ij_device(int32_t probe_side, int64_t n_p, const int64_t* d_pkey, const int6
 struct gw_ijoin {
     gw_ijoin_config cfg{};
     IjBounds b{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    hipEvent_t ev_t[4] = {};  // the last pass: probe stage begin / end, merge begin / end
+    OpError er{kIjName};
+    OpStream os;
+    TimedPair probe_t, merge_t;  // the last pass: around its probe stage and around its merge
     bool timed = false;
     DevCols<3> log[2], alt[2], stage;  // alt: the buffer the next merge or eviction writes
     int64_t n_log[2] = {0, 0};
-    DevCols<5> out;
-    int64_t out_from = 0, pending = 0;
+    RowBuf rows{false};  // the pending rows
+    // the passes' scratch; the stream is idle before a block it may still use is freed
     DevBuf<char> scr;
     int64_t wm = INT64_MIN, late = 0, max_batch = 0;
-    bool failed = false;
-    std::string err;
     gw_ijoin_stats st{};
 
-    int fail(int rc, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        if (rc != GW_E_OUTPUT_FULL && rc != GW_E_INVALID) failed = true;
-        return rc;
-    }
-    int dev_fail(hipError_t e) { return fail(GW_E_DEVICE, "interval join: %s", hipGetErrorString(e)); }
-
-    // the pass's scratch; the stream is idle before a block it may still use is freed
-    int scratch(size_t need) {
-        if ((int64_t)need <= scr.cap) return GW_OK;
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return dev_fail(e);
-        if (scr.reserve_discard((int64_t)need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GW_E_OOM, "interval join: out of device memory");
-        }
-        return GW_OK;
-    }
-    int reserve_out(int64_t more) {
-        if (out_from + pending + more <= out.cap) return GW_OK;
-        const int64_t cap = std::max<int64_t>(pending + more, 2 * out.cap);
-        if (out.reserve_keep(cap, out_from, pending, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GW_E_OOM, "interval join: out of device memory for %lld pending rows", (long long)(pending + more));
-        }
-        out_from = 0;
-        return GW_OK;
-    }
     // alt[side] with room for `need` rows; grow: a log that outgrows its capacity doubles
     int reserve_alt(int side, int64_t need, bool grow) {
         if (need <= alt[side].cap) return GW_OK;
         const int64_t cap = grow ? std::max<int64_t>(need, 2 * std::max(log[side].cap, alt[side].cap)) : std::max(need, log[side].cap);
-        if (alt[side].reserve_keep(cap, 0, 0, stream) != hipSuccess) {
+        if (alt[side].reserve_keep(cap, 0, 0, os.stream) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(GW_E_OOM, "interval join: out of device memory for the %s log", side ? "right" : "left");
+            return er.fail(GW_E_OOM, "interval join: out of device memory for the %s log", side ? "right" : "left");
         }
         if (grow) ++st.log_growths;
         return GW_OK;
@@ -630,78 +558,73 @@ struct gw_ijoin {
     // of the call behind (device columns, ordered behind their producer).
     int check_call(int side, int64_t n, const int64_t* key, const int64_t* ts) {
         IjFilterArrays F;
-        Carve size{nullptr};
-        F.carve(size, 1);
-        int rc = scratch(size.at);
+        int rc = carve_from([&](Carve& c) { F.carve(c, 1); }, scr, er, os.stream);
         if (rc) return rc;
-        Carve cv{scr.p};
-        F.carve(cv, 1);
-        hipLaunchKernelGGL(k_ij_hdr_init, dim3(1), dim3(kJoinThreads), 0, stream, F.hdr);
-        hipLaunchKernelGGL(k_ij_filter, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, key, ts, side, b, wm,
+        hipLaunchKernelGGL(k_ij_hdr_init, dim3(1), dim3(kJoinThreads), 0, os.stream, F.hdr);
+        hipLaunchKernelGGL(k_ij_filter, dim3(grid_for(n)), dim3(kJoinThreads), 0, os.stream, n, key, ts, side, b, wm,
                            (uint32_t*)nullptr, F.hdr);
         int64_t h[kIjHdr];
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, F.hdr, sizeof h, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return dev_fail(e);
+        if (e == hipSuccess) e = read_hdr(h, F.hdr, kIjHdr, os.stream);
+        if (e != hipSuccess) return er.dev_fail(e);
         std::string why;
-        if ((rc = ij_flag_error((uint64_t)h[IH_FLAGS], why))) return fail(rc, "%s", why.c_str());
+        if ((rc = ij_flag_error((uint64_t)h[IH_FLAGS], why))) return er.fail(rc, "%s", why.c_str());
         return GW_OK;
     }
 
     // One pass: m records of `side` in device columns, already ordered behind their producer.
     // The columns are free once this returns.
-    int pass(int side, int64_t m, const int64_t* key, const int64_t* ts, const int64_t* pay, int64_t* rows) {
+    int pass(int side, int64_t m, const int64_t* key, const int64_t* ts, const int64_t* pay, int64_t* made) {
+        hipStream_t stream = os.stream;
         IjArrays A;
-        Carve size{nullptr};
-        A.carve(size, m, true);
-        int rc = scratch(size.at);
+        int rc = carve_from([&](Carve& c) { A.carve(c, m, true); }, scr, er, os.stream);
         if (rc) return rc;
-        Carve cv{scr.p};
-        A.carve(cv, m, true);
         int64_t h[kIjHdr];
         hipError_t e = ij_launch_filter(m, key, ts, pay, side, b, wm, A, A.c, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h, A.hdr, sizeof h, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return dev_fail(e);
+        if (e == hipSuccess) e = read_hdr(h, A.hdr, kIjHdr, stream);
+        if (e != hipSuccess) return er.dev_fail(e);
         std::string why;
-        if ((rc = ij_flag_error((uint64_t)h[IH_FLAGS], why))) return fail(rc, "%s", why.c_str());
+        if ((rc = ij_flag_error((uint64_t)h[IH_FLAGS], why))) return er.fail(rc, "%s", why.c_str());
         const int64_t kept = h[IH_KEPT];
         late += h[IH_LATE];
         if (kept == 0) return GW_OK;
         if (n_log[side] + kept > kSortMaxRecords)
-            return fail(GW_E_UNSUPPORTED, "interval join: more than 2^30 - 1 live records on one side");
-        if ((e = ij_sort(A, kept, h, stream)) != hipSuccess) return dev_fail(e);
+            return er.fail(GW_E_UNSUPPORTED, "interval join: more than 2^30 - 1 live records on one side");
+        if ((e = ij_sort(A, kept, h, stream)) != hipSuccess) return er.dev_fail(e);
         timed = true;
-        (void)hipEventRecord(ev_t[0], stream);
+        probe_t.begin(stream);
         const IjLog other = side_log(1 - side);
         if (other.n > 0) {
             e = ij_launch_probe(A, kept, side, b, other, stream);
             if (e == hipSuccess) e = hipMemcpyAsync(h, A.hdr, sizeof h, hipMemcpyDeviceToHost, stream);
-            (void)hipEventRecord(ev_t[1], stream);
+            probe_t.end(stream);
             if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return dev_fail(e);
+            if (e != hipSuccess) return er.dev_fail(e);
             const int64_t P = h[IH_P], nc = h[IH_NC];
-            if (P > kIjMaxRows - pending) return fail(GW_E_RANGE, "interval join: the pending rows exceed int64 bytes");
+            if (P > kIjMaxRows - rows.pending) return er.fail(GW_E_RANGE, "interval join: the pending rows exceed int64 bytes");
             if (P > 0) {
-                if ((rc = reserve_out(P))) return rc;
+                if (rows.reserve(P, stream) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return er.fail(GW_E_OOM, "interval join: out of device memory for %lld pending rows",
+                                   (long long)(rows.pending + P));
+                }
                 IjOut o;
-                for (int c = 0; c < 5; ++c) o.col[c] = out[c] + out_from + pending;
-                if ((e = ij_launch_expand(A, P, nc, side, other, o, stream)) != hipSuccess) return dev_fail(e);
-                pending += P;
-                *rows += P;
+                rows.tail(o.col);
+                if ((e = ij_launch_expand(A, P, nc, side, other, o, stream)) != hipSuccess) return er.dev_fail(e);
+                rows.pending += P;
+                *made += P;
             }
         } else {
-            (void)hipEventRecord(ev_t[1], stream);
+            probe_t.end(stream);
         }
         // the batch joins its own side's log, in the log's other buffer
         const int64_t need = n_log[side] + kept;
         if ((rc = reserve_alt(side, need, true))) return rc;
-        (void)hipEventRecord(ev_t[2], stream);
+        merge_t.begin(stream);
         hipLaunchKernelGGL(k_ij_merge, dim3(grid_for(need)), dim3(kJoinThreads), 0, stream, A.sorted(kept), side_log(side),
                            alt[side][0], alt[side][1], alt[side][2]);
-        (void)hipEventRecord(ev_t[3], stream);
-        if ((e = hipGetLastError()) != hipSuccess) return dev_fail(e);
+        merge_t.end(stream);
+        if ((e = hipGetLastError()) != hipSuccess) return er.dev_fail(e);
         std::swap(log[side], alt[side]);
         n_log[side] = need;
         ++st.merges;
@@ -710,27 +633,23 @@ struct gw_ijoin {
 
     int advance(int64_t w) {
         if (w <= wm) return GW_OK;  // a watermark that does not advance is ignored
+        hipStream_t stream = os.stream;
         for (int sd = 0; sd < 2; ++sd) {
             const int64_t n = n_log[sd];
             if (n == 0) continue;
             IjFilterArrays F;
-            Carve size{nullptr};
-            F.carve(size, n);
-            int rc = scratch(size.at);
+            int rc = carve_from([&](Carve& c) { F.carve(c, n); }, scr, er, os.stream);
             if (rc) return rc;
-            Carve cv{scr.p};
-            F.carve(cv, n);
             if ((rc = reserve_alt(sd, n, false))) return rc;
             hipLaunchKernelGGL(k_ij_evict_flags, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, log[sd][1], sd, b, w, F.keep);
             hipError_t e = scan_excl<uint32_t, uint32_t>(F.keep, F.koff, n, F.blk, F.hdr + IH_KEPT, stream);
-            if (e != hipSuccess) return dev_fail(e);
-            IjCols c{{log[sd][0], log[sd][1], log[sd][2]}, {alt[sd][0], alt[sd][1], alt[sd][2]}};
-            hipLaunchKernelGGL(k_ij_compact3, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, F.keep, F.koff, c);
+            if (e != hipSuccess) return er.dev_fail(e);
+            Cols3 c{{log[sd][0], log[sd][1], log[sd][2]}, {alt[sd][0], alt[sd][1], alt[sd][2]}};
+            hipLaunchKernelGGL(k_compact3, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, F.keep, F.koff, c);
             int64_t kept = 0;
             e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&kept, F.hdr + IH_KEPT, 8, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return dev_fail(e);
+            if (e == hipSuccess) e = read_hdr(&kept, F.hdr + IH_KEPT, 1, stream);
+            if (e != hipSuccess) return er.dev_fail(e);
             std::swap(log[sd], alt[sd]);
             n_log[sd] = kept;
         }
@@ -844,18 +763,14 @@ int gw_ijoin_create(const gw_ijoin_config* cfg, gw_ijoin** out) {
     h->cfg = *cfg;
     h->b = IjBounds{cfg->lower, cfg->upper};
     h->max_batch = cfg->max_batch > 0 ? std::min<int64_t>(cfg->max_batch, kSortMaxRecords) : (int64_t)1 << 22;
-    hipError_t e = hipSetDevice(cfg->device);
-    if (e != hipSuccess) return bail(GW_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail(GW_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-    if ((e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming)) != hipSuccess)
+    const char* what;
+    hipError_t e = h->os.create(cfg->device, &what);
+    if (e != hipSuccess) return bail(GW_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    if ((e = h->probe_t.create()) != hipSuccess || (e = h->merge_t.create()) != hipSuccess)
         return bail(GW_E_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(e));
-    for (auto& ev : h->ev_t)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(GW_E_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(e));
     const int64_t cap0 = std::max<int64_t>(cfg->capacity_hint, 16);
     for (int sd = 0; sd < 2; ++sd)
-        if (h->log[sd].reserve_keep(cap0, 0, 0, h->stream) != hipSuccess || h->alt[sd].reserve_keep(cap0, 0, 0, h->stream) != hipSuccess)
+        if (h->log[sd].reserve_keep(cap0, 0, 0, h->os.stream) != hipSuccess || h->alt[sd].reserve_keep(cap0, 0, 0, h->os.stream) != hipSuccess)
             return bail(GW_E_OOM, "interval join: out of device memory");
     *out = h;
     return GW_OK;
@@ -863,43 +778,14 @@ int gw_ijoin_create(const gw_ijoin_config* cfg, gw_ijoin** out) {
 
 int gw_ijoin_destroy(gw_ijoin* h) {
     if (!h) return GW_OK;
-    hipSetDevice(h->cfg.device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->ev_in) hipEventDestroy(h->ev_in);
-    if (h->ev_out) hipEventDestroy(h->ev_out);
-    for (auto ev : h->ev_t)
-        if (ev) hipEventDestroy(ev);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    h->os.destroy();
+    delete h;  // (the timing events go with it: the stream they were recorded on has been waited for)
     return GW_OK;
 }
 
-const char* gw_ijoin_last_error(const gw_ijoin* h) { return h ? h->err.c_str() : gw_last_error(nullptr); }
+const char* gw_ijoin_last_error(const gw_ijoin* h) { return h ? h->er.err.c_str() : gw_last_error(nullptr); }
 
-#define IJOIN_ENTER(h)                                                                    \
-    if (!(h)) return GW_E_INVALID;                                                        \
-    if ((h)->failed) return GW_E_STATE;                                                   \
-    hipSetDevice((h)->cfg.device)
-
-int gw_ijoin_ingest_device(gw_ijoin* h, int32_t side, int64_t n, const int64_t* d_key, const int64_t* d_ts,
-                           const int64_t* d_payload, void* stream, int64_t* rows) {
-    IJOIN_ENTER(h);
-    if (rows) *rows = 0;
-    if ((side != GW_JOIN_LEFT && side != GW_JOIN_RIGHT) || n < 0 || (n > 0 && (!d_key || !d_ts || !d_payload)))
-        return h->fail(GW_E_INVALID, "gw_ijoin_ingest_device: bad side or null column");
-    hipStream_t ps = (hipStream_t)stream;
-    if (ps != h->stream) {
-        hipEventRecord(h->ev_in, ps);
-        hipStreamWaitEvent(h->stream, h->ev_in, 0);
-    }
-    int64_t made = 0;
-    int rc = n > h->max_batch ? h->check_call(side, n, d_key, d_ts) : GW_OK;
-    for (int64_t at = 0; at < n && rc == GW_OK; at += h->max_batch)
-        rc = h->pass(side, std::min(h->max_batch, n - at), d_key + at, d_ts + at, d_payload + at, &made);
-    if (ps != h->stream) {
-        hipEventRecord(h->ev_out, h->stream);
-        hipStreamWaitEvent(ps, h->ev_out, 0);
-    }
+static int ij_ingested(gw_ijoin* h, int rc, int64_t made, int64_t* rows) {
     if (rc) return rc;
     h->st.rows_emitted += made;
     h->st.last_call_rows = made;
@@ -907,12 +793,26 @@ int gw_ijoin_ingest_device(gw_ijoin* h, int32_t side, int64_t n, const int64_t* 
     return GW_OK;
 }
 
+int gw_ijoin_ingest_device(gw_ijoin* h, int32_t side, int64_t n, const int64_t* d_key, const int64_t* d_ts,
+                           const int64_t* d_payload, void* stream, int64_t* rows) {
+    GW_OP_ENTER(h);
+    if (rows) *rows = 0;
+    if ((side != GW_JOIN_LEFT && side != GW_JOIN_RIGHT) || n < 0 || (n > 0 && (!d_key || !d_ts || !d_payload)))
+        return h->er.fail(GW_E_INVALID, "gw_ijoin_ingest_device: bad side or null column");
+    OpStream::Handoff handoff(h->os, (hipStream_t)stream, n > 0);
+    int64_t made = 0;
+    int rc = n > h->max_batch ? h->check_call(side, n, d_key, d_ts) : GW_OK;
+    for (int64_t at = 0; at < n && rc == GW_OK; at += h->max_batch)
+        rc = h->pass(side, std::min(h->max_batch, n - at), d_key + at, d_ts + at, d_payload + at, &made);
+    return ij_ingested(h, rc, made, rows);
+}
+
 int gw_ijoin_ingest(gw_ijoin* h, int32_t side, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* payload,
                     int64_t* rows) {
-    IJOIN_ENTER(h);
+    GW_OP_ENTER(h);
     if (rows) *rows = 0;
     if ((side != GW_JOIN_LEFT && side != GW_JOIN_RIGHT) || n < 0 || (n > 0 && (!key || !ts || !payload)))
-        return h->fail(GW_E_INVALID, "gw_ijoin_ingest: bad side or null column");
+        return h->er.fail(GW_E_INVALID, "gw_ijoin_ingest: bad side or null column");
     if (n > h->max_batch) {  // several passes: the checks over the whole call first
         uint64_t flags = 0;
         for (int64_t i = 0; i < n; ++i) {
@@ -921,84 +821,58 @@ int gw_ijoin_ingest(gw_ijoin* h, int32_t side, int64_t n, const int64_t* key, co
         }
         std::string why;
         const int rc = ij_flag_error(flags, why);
-        if (rc) return h->fail(rc, "%s", why.c_str());
+        if (rc) return h->er.fail(rc, "%s", why.c_str());
     }
     int64_t made = 0;
-    for (int64_t at = 0; at < n; at += h->max_batch) {
-        const int64_t m = std::min(h->max_batch, n - at);
-        if (h->stage.cap < m && h->stage.reserve_keep(m, 0, 0, h->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return h->fail(GW_E_OOM, "interval join: out of device memory staging a batch");
-        }
-        const int64_t* src[3] = {key + at, ts + at, payload + at};
-        for (int c = 0; c < 3; ++c) {
-            const hipError_t e = hipMemcpyAsync(h->stage[c], src[c], (size_t)m * 8, hipMemcpyHostToDevice, h->stream);
-            if (e != hipSuccess) return h->dev_fail(e);
-        }
-        // (the pass waits for the stream behind its filter, so the host columns and the staging
-        // columns are free when it returns)
-        const int rc = h->pass(side, m, h->stage[0], h->stage[1], h->stage[2], &made);
-        if (rc) return rc;
-    }
-    h->st.rows_emitted += made;
-    h->st.last_call_rows = made;
-    if (rows) *rows = made;
-    return GW_OK;
+    const int64_t* src[3] = {key, ts, payload};
+    // (the pass waits for the stream behind its filter, so the host columns and the staging
+    // columns are free when it returns)
+    const int rc = staged_ingest(h->stage, h->max_batch, n, src, h->os.stream, h->er,
+                                 [&](int64_t m, int64_t* const* d) { return h->pass(side, m, d[0], d[1], d[2], &made); });
+    return ij_ingested(h, rc, made, rows);
 }
 
 int gw_ijoin_advance_watermark(gw_ijoin* h, int64_t watermark) {
-    IJOIN_ENTER(h);
+    GW_OP_ENTER(h);
     return h->advance(watermark);
 }
 
 int gw_ijoin_end_input(gw_ijoin* h) {
-    IJOIN_ENTER(h);
+    GW_OP_ENTER(h);
     return h->advance(INT64_MAX);
 }
 
 int gw_ijoin_pending(gw_ijoin* h, int64_t* n) {
-    IJOIN_ENTER(h);
-    if (!n) return h->fail(GW_E_INVALID, "gw_ijoin_pending: null argument");
-    *n = h->pending;
+    GW_OP_ENTER(h);
+    if (!n) return h->er.fail(GW_E_INVALID, "gw_ijoin_pending: null argument");
+    *n = h->rows.pending;
     return GW_OK;
 }
 
 int gw_ijoin_drain(gw_ijoin* h, int64_t* key, int64_t* lts, int64_t* rts, int64_t* lpay, int64_t* rpay, int64_t cap,
                    int64_t* n) {
-    IJOIN_ENTER(h);
+    GW_OP_ENTER(h);
     if (!n || cap < 0 || (cap > 0 && (!key || !lts || !rts || !lpay || !rpay)))
-        return h->fail(GW_E_INVALID, "gw_ijoin_drain: bad argument");
-    const int64_t m = std::min(cap, h->pending);
-    *n = m;
-    int64_t* dst[5] = {key, lts, rts, lpay, rpay};
-    hipError_t e = hipSuccess;
-    for (int c = 0; c < 5 && m > 0 && e == hipSuccess; ++c)
-        e = hipMemcpyAsync(dst[c], h->out[c] + h->out_from, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return h->dev_fail(e);
-    h->out_from += m;
-    h->pending -= m;
-    if (h->pending == 0) h->out_from = 0;
-    return h->pending > 0 ? GW_E_OUTPUT_FULL : GW_OK;
+        return h->er.fail(GW_E_INVALID, "gw_ijoin_drain: bad argument");
+    int64_t* const dst[5] = {key, lts, rts, lpay, rpay};
+    return h->rows.drain(dst, nullptr, cap, n, h->os.stream, h->er);
 }
 
 int gw_ijoin_rows_device(gw_ijoin* h, const int64_t** d_key, const int64_t** d_lts, const int64_t** d_rts,
                          const int64_t** d_lpay, const int64_t** d_rpay, int64_t* n) {
-    IJOIN_ENTER(h);
-    if (!d_key || !d_lts || !d_rts || !d_lpay || !d_rpay || !n) return h->fail(GW_E_INVALID, "gw_ijoin_rows_device: null argument");
+    GW_OP_ENTER(h);
+    if (!d_key || !d_lts || !d_rts || !d_lpay || !d_rpay || !n) return h->er.fail(GW_E_INVALID, "gw_ijoin_rows_device: null argument");
     // (an ingest returns with its expand kernel in flight: the view is of finished rows)
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return h->dev_fail(e);
-    const int64_t** dst[5] = {d_key, d_lts, d_rts, d_lpay, d_rpay};
-    for (int c = 0; c < 5; ++c) *dst[c] = h->pending ? h->out[c] + h->out_from : nullptr;
-    *n = h->pending;
+    const hipError_t e = hipStreamSynchronize(h->os.stream);
+    if (e != hipSuccess) return h->er.dev_fail(e);
+    const int64_t** const dst[5] = {d_key, d_lts, d_rts, d_lpay, d_rpay};
+    h->rows.view(dst, nullptr, n);
     return GW_OK;
 }
 
 int gw_ijoin_clear_rows(gw_ijoin* h) {
-    IJOIN_ENTER(h);
-    h->pending = 0;
-    h->out_from = 0;
+    GW_OP_ENTER(h);
+    h->rows.clear();
     return GW_OK;
 }
 
@@ -1015,16 +889,16 @@ int gw_ijoin_get_stats(const gw_ijoin* h, gw_ijoin_stats* out) {
 }
 
 int gw_ijoin_last_times(gw_ijoin* h, double* probe_ms, double* merge_ms) {
-    IJOIN_ENTER(h);
-    if (!probe_ms || !merge_ms) return h->fail(GW_E_INVALID, "gw_ijoin_last_times: null argument");
+    GW_OP_ENTER(h);
+    if (!probe_ms || !merge_ms) return h->er.fail(GW_E_INVALID, "gw_ijoin_last_times: null argument");
     *probe_ms = *merge_ms = 0;
     if (!h->timed) return GW_OK;
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return h->dev_fail(e);
+    hipError_t e = hipStreamSynchronize(h->os.stream);
+    if (e != hipSuccess) return h->er.dev_fail(e);
     float p = 0, m = 0;
-    if ((e = hipEventElapsedTime(&p, h->ev_t[0], h->ev_t[1])) != hipSuccess) return h->dev_fail(e);
+    if ((e = h->probe_t.elapsed(&p)) != hipSuccess) return h->er.dev_fail(e);
     // (a pass that kept nothing, or failed before its merge, leaves the merge's events of an earlier pass)
-    if (hipEventElapsedTime(&m, h->ev_t[2], h->ev_t[3]) != hipSuccess) {
+    if (h->merge_t.elapsed(&m) != hipSuccess) {
         (void)hipGetLastError();
         m = 0;
     }
@@ -1033,6 +907,6 @@ int gw_ijoin_last_times(gw_ijoin* h, double* probe_ms, double* merge_ms) {
     return GW_OK;
 }
 
-void* gw_ijoin_stream(gw_ijoin* h) { return h ? (void*)h->stream : nullptr; }
+void* gw_ijoin_stream(gw_ijoin* h) { return h ? (void*)h->os.stream : nullptr; }
 
 }  // extern "C"

@@ -40,8 +40,6 @@
 // a down-sweep); the only look-back is gw_sort.hip's own.  The host reads the device twice per
 // call: the tuple count (it sizes the sort) and the pair count (it sizes the output).
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -49,8 +47,8 @@
 #include <string>
 #include <vector>
 
-#include "gw_devmem.h"
-#include "gw_joinutil.h"  // scan_excl, the wave reductions and search, Scratch, Carve
+#include "gw_joinop.h"    // the host side of the operator: OpError, OpStream, RowBuf, staged_ingest (and gw_devmem.h)
+#include "gw_joinutil.h"  // scan_excl, the wave reductions and search, k_compact3, Scratch, Carve
 #include "gw_kernels.h"
 #include "gw_sort.h"
 
@@ -60,6 +58,7 @@ struct JoinGeom {
     int64_t size, slide, offset;
 };
 
+constexpr const char* kJoinName = "window join";  // the prefix of the shared helpers' messages
 constexpr uint32_t kJoinRight = 0x80000000u;
 // header words (int64) shared by the stages of one call
 enum { JH_NT = 0, JH_MINS, JH_MAXS, JH_MINK, JH_MAXK, JH_FLAGS, JH_NG, JH_TOTAL, JH_NC, JH_KEPT, JH_LATE, kJoinHdr = 16 };
@@ -527,10 +526,6 @@ typedef std::function<int(int64_t, JoinOut&, std::string&)> JoinProvide;
 // provide(groups, left elements, right elements, out): the caller's CSR columns (or an error).
 typedef std::function<int(int64_t, int64_t, int64_t, CoGroupOut&, std::string&)> CoGroupProvide;
 
-struct JoinTimes {  // HIP events around the expand kernel or the coGroup writers (scripts/join_bench.py)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-
 // One call at a time per process: every call waits for its launches before it returns, so the
 // per-device scratch is free for the next.
 static std::mutex g_join_mu;
@@ -542,10 +537,6 @@ struct JoinStage {  // what stages count .. groups leave behind (g_join_mu held)
     int64_t nt = 0, min_start = 0;
     int64_t h[kJoinHdr];
 };
-static int join_dev_fail(hipError_t e, std::string& why) {
-    why = std::string("window join: ") + hipGetErrorString(e);
-    return GW_E_DEVICE;
-}
 
 // Stages count, emit, sort and groups: the sorted tuples (gkey, gord, gsrc, gpay) and the group
 // table (head, hex, gfirst, gmid; hdr[JH_NG] groups, on the device).  st.nt = 0: nothing fired.
@@ -556,18 +547,13 @@ static int join_groups(const JoinIn& a, JoinStage& st, int64_t* n_tuples, hipStr
     RecArrays& R = st.R;
     TupArrays& T = st.T;
     int64_t* h = st.h;
-    Carve size_r{nullptr};
-    R.carve(size_r, a.n);
-    int rc = scratch_ensure(g_scr_rec[dev], size_r.at, why);
+    int rc = carve_from([&](Carve& c) { R.carve(c, a.n); }, g_scr_rec[dev], kJoinName, why);
     if (rc) return rc;
-    Carve cr{g_scr_rec[dev].p};
-    R.carve(cr, a.n);
     hipLaunchKernelGGL(k_join_hdr_init, dim3(1), dim3(kJoinThreads), 0, s, R.hdr);
     hipLaunchKernelGGL(k_join_count, dim3(grid_for(a.n)), dim3(kJoinThreads), 0, s, a, R.cnt, R.hdr);
     hipError_t e = scan_excl<uint32_t, uint32_t>(R.cnt, R.toff, a.n, R.blk, R.hdr + JH_NT, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof st.h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return join_dev_fail(e, why);
+    if (e == hipSuccess) e = read_hdr(h, R.hdr, kJoinHdr, s);
+    if (e != hipSuccess) return dev_fail(kJoinName, e, why);
     if (h[JH_FLAGS] & GW_DF_NO_TS) {
         why = "Record has Long.MIN_VALUE timestamp (= no timestamp marker)";
         return GW_E_NO_TIMESTAMP;
@@ -585,35 +571,31 @@ static int join_groups(const JoinIn& a, JoinStage& st, int64_t* n_tuples, hipStr
     const uint64_t min_kw = (uint64_t)h[JH_MINK];
     const int kbits = bit_length((uint64_t)h[JH_MAXK] - min_kw);
     const int obits = bit_length(((uint64_t)h[JH_MAXS] - (uint64_t)min_start) / (uint64_t)a.g.slide);
-    Carve size_t_{nullptr};
-    T.carve(size_t_, nt);
-    if ((rc = scratch_ensure(g_scr_tup[dev], size_t_.at, why))) return rc;
-    Carve ct{g_scr_tup[dev].p};
-    T.carve(ct, nt);
+    if ((rc = carve_from([&](Carve& c) { T.carve(c, nt); }, g_scr_tup[dev], kJoinName, why))) return rc;
     const int gt = grid_for(nt);
     hipLaunchKernelGGL(k_join_emit, dim3(grid_for(a.n)), dim3(kJoinThreads), 0, s, a, R.toff, min_start, min_kw, T.kw0, T.ord,
                        T.src);
-    if ((e = hipGetLastError()) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = hipGetLastError()) != hipSuccess) return dev_fail(kJoinName, e, why);
     // by key word, then by window ordinal: both stable, so a group keeps left before right and
     // each side its arrival order
     int alt = 0;
     if ((e = sort_pairs_u64(T.kw0, T.v0, T.kw1, T.v1, nt, 0, kbits, T.sort, s, &alt, true)) != hipSuccess)
-        return join_dev_fail(e, why);
+        return dev_fail(kJoinName, e, why);
     uint32_t* perm = alt ? T.v1 : T.v0;
     if (obits > 0) {
         uint32_t* other = alt ? T.v0 : T.v1;
         hipLaunchKernelGGL(k_join_gather_ord, dim3(gt), dim3(kJoinThreads), 0, s, nt, perm, T.ord, T.ord0);
         if ((e = sort_pairs_u64(T.ord0, perm, T.ord1, other, nt, 0, obits, T.sort, s, &alt, false)) != hipSuccess)
-            return join_dev_fail(e, why);
+            return dev_fail(kJoinName, e, why);
         if (alt) perm = other;
     }
     hipLaunchKernelGGL(k_join_gather, dim3(gt), dim3(kJoinThreads), 0, s, a, nt, perm, T.ord, T.src, T.gkey, T.gord, T.gsrc,
                        T.gpay);
     hipLaunchKernelGGL(k_join_heads, dim3(gt), dim3(kJoinThreads), 0, s, nt, T.gkey, T.gord, T.head);
-    if ((e = scan_excl<uint32_t, uint32_t>(T.head, T.hex, nt, T.blk, R.hdr + JH_NG, s)) != hipSuccess) return join_dev_fail(e, why);
-    if ((e = hipMemsetAsync(T.gmid, 0xFF, (size_t)nt * 4, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = scan_excl<uint32_t, uint32_t>(T.head, T.hex, nt, T.blk, R.hdr + JH_NG, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
+    if ((e = hipMemsetAsync(T.gmid, 0xFF, (size_t)nt * 4, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
     hipLaunchKernelGGL(k_join_group_fill, dim3(gt), dim3(kJoinThreads), 0, s, nt, T.head, T.hex, T.gsrc, T.gfirst, T.gmid);
-    if ((e = hipGetLastError()) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = hipGetLastError()) != hipSuccess) return dev_fail(kJoinName, e, why);
     return GW_OK;
 }
 
@@ -631,7 +613,7 @@ static void launch_expand(bool vec, int64_t nblk, hipStream_t s, int64_t total, 
 // mode: GW_JOIN_MODE_INNER .. FULL_OUTER; the rows carry null_payload for a lacking side, and
 // out.present (when provide leaves one) says which sides a row has.  max_rows: the byte bound.
 int join_run(const JoinIn& a, int mode, int64_t null_payload, int64_t max_rows, const JoinProvide& provide,
-             int64_t* n_pairs, int64_t* n_tuples, hipStream_t s, std::string& why, const JoinTimes* times = nullptr) {
+             int64_t* n_pairs, int64_t* n_tuples, hipStream_t s, std::string& why, const TimedPair& times = TimedPair()) {
     *n_pairs = 0;
     std::lock_guard<std::mutex> lock(g_join_mu);
     JoinStage st;
@@ -648,14 +630,13 @@ int join_run(const JoinIn& a, int mode, int64_t null_payload, int64_t max_rows, 
     const int gt = grid_for(nt);
     hipError_t e;
     hipLaunchKernelGGL(k_join_group_prod, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, mode, T.prod, T.ne);
-    if ((e = scan_excl<int64_t, int64_t>(T.prod, T.poff, nt, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return join_dev_fail(e, why);
-    if ((e = scan_excl<uint32_t, uint32_t>(T.ne, T.cidx, nt, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = scan_excl<int64_t, int64_t>(T.prod, T.poff, nt, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
+    if ((e = scan_excl<uint32_t, uint32_t>(T.ne, T.cidx, nt, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
     hipLaunchKernelGGL(k_join_compact, dim3(gt), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, T.prod, T.poff, T.cidx,
                        T.gkey, T.gord, st.min_start, a.g.slide, T.coff, T.cfirst, T.crb, T.cR, T.ckey, T.cws);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof st.h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return join_dev_fail(e, why);
+    if (e == hipSuccess) e = read_hdr(h, R.hdr, kJoinHdr, s);
+    if (e != hipSuccess) return dev_fail(kJoinName, e, why);
     const int64_t total = h[JH_TOTAL], nc = h[JH_NC];
     if (total > max_rows) { why = "window join: the pairs of one fire exceed int64 bytes"; return GW_E_RANGE; }
     *n_pairs = total;
@@ -663,17 +644,12 @@ int join_run(const JoinIn& a, int mode, int64_t null_payload, int64_t max_rows, 
     if ((rc = provide(total, out, why))) return rc;
     if (total == 0) return GW_OK;
     out.null_payload = null_payload;
-    // two rows per 16-byte store need the five columns at one alignment
-    int par[5];
-    for (int c = 0; c < 5; ++c) par[c] = (int)(((uintptr_t)out.col[c] >> 3) & 1);
-    const bool vec = par[0] == par[1] && par[0] == par[2] && par[0] == par[3] && par[0] == par[4] &&
-                     !((uintptr_t)out.col[0] & 7);
-    const int shift = vec ? par[0] : 0;
+    const auto [vec, shift] = expand_alignment(out.col);
     const int64_t nblk = (total + shift + kExpTile - 1) / kExpTile;
-    if (times) (void)hipEventRecord(times->e0, s);
+    times.begin(s);
     switch (mode) {
         case GW_JOIN_MODE_INNER:  // every row has both sides
-            if (out.present && (e = hipMemsetAsync(out.present, 3, (size_t)total, s)) != hipSuccess) return join_dev_fail(e, why);
+            if (out.present && (e = hipMemsetAsync(out.present, 3, (size_t)total, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
             launch_expand<GW_JOIN_MODE_INNER>(vec, nblk, s, total, shift, nc, T, a.g.size, out);
             break;
         case GW_JOIN_MODE_LEFT_OUTER: launch_expand<GW_JOIN_MODE_LEFT_OUTER>(vec, nblk, s, total, shift, nc, T, a.g.size, out); break;
@@ -681,15 +657,15 @@ int join_run(const JoinIn& a, int mode, int64_t null_payload, int64_t max_rows, 
         default: launch_expand<GW_JOIN_MODE_FULL_OUTER>(vec, nblk, s, total, shift, nc, T, a.g.size, out); break;
     }
     e = hipGetLastError();
-    if (times) (void)hipEventRecord(times->e1, s);
+    times.end(s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // the scratch is free for the next call
-    if (e != hipSuccess) return join_dev_fail(e, why);
+    if (e != hipSuccess) return dev_fail(kJoinName, e, why);
     return GW_OK;
 }
 
 // The fired groups as a CSR: n[0] groups, n[1] left and n[2] right elements.
 int cogroup_run(const JoinIn& a, const CoGroupProvide& provide, int64_t* n, int64_t* n_tuples, hipStream_t s,
-                std::string& why, const JoinTimes* times = nullptr) {
+                std::string& why, const TimedPair& times = TimedPair()) {
     n[0] = n[1] = n[2] = 0;
     std::lock_guard<std::mutex> lock(g_join_mu);
     JoinStage st;
@@ -705,28 +681,27 @@ int cogroup_run(const JoinIn& a, const CoGroupProvide& provide, int64_t* n, int6
     int64_t *loff = T.poff, *roff = T.coff;
     hipError_t e;
     hipLaunchKernelGGL(k_cogroup_sizes, dim3(grid_for(nt + 1)), dim3(kJoinThreads), 0, s, nt, R.hdr, T.gfirst, T.gmid, gl, gr);
-    if ((e = scan_excl<uint32_t, int64_t>(gl, loff, nt + 1, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return join_dev_fail(e, why);
-    if ((e = scan_excl<uint32_t, int64_t>(gr, roff, nt + 1, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return join_dev_fail(e, why);
-    if ((e = hipMemcpyAsync(h, R.hdr, sizeof st.h, hipMemcpyDeviceToHost, s)) != hipSuccess) return join_dev_fail(e, why);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return join_dev_fail(e, why);
+    if ((e = scan_excl<uint32_t, int64_t>(gl, loff, nt + 1, T.blk, R.hdr + JH_TOTAL, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
+    if ((e = scan_excl<uint32_t, int64_t>(gr, roff, nt + 1, T.blk, R.hdr + JH_NC, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
+    if ((e = read_hdr(h, R.hdr, kJoinHdr, s)) != hipSuccess) return dev_fail(kJoinName, e, why);
     const int64_t ng = h[JH_NG];
     n[0] = ng;
     n[1] = h[JH_TOTAL];
     n[2] = h[JH_NC];
     if ((rc = provide(n[0], n[1], n[2], out, why))) return rc;
-    if (times) (void)hipEventRecord(times->e0, s);
+    times.begin(s);
     hipLaunchKernelGGL(k_cogroup_groups, dim3(grid_for(ng + 1)), dim3(kJoinThreads), 0, s, R.hdr, T.gfirst, T.gkey, T.gord,
                        st.min_start, a.g.slide, a.g.size, loff, roff, out);
     hipLaunchKernelGGL(k_cogroup_elems, dim3(grid_for(nt)), dim3(kJoinThreads), 0, s, nt, T.head, T.hex, T.gsrc, T.gfirst,
                        T.gmid, T.gpay, loff, roff, out);
     e = hipGetLastError();
-    if (times) (void)hipEventRecord(times->e1, s);
+    times.end(s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // the scratch is free for the next call
-    if (e != hipSuccess) return join_dev_fail(e, why);
+    if (e != hipSuccess) return dev_fail(kJoinName, e, why);
     return GW_OK;
 }
 
-// ---- operator state: late filter and stable compaction -------------------------------------
+// ---- operator state: the late filter (the stable compaction behind it is k_compact3) ---------
 // keep[i] = 1 for the records that stay: at ingest those with a window still open at wm (the
 // others are late, counted in hdr[JH_LATE]); after a fire the same test at the new watermark.
 __global__ void __launch_bounds__(kJoinThreads) k_join_filter(int64_t n, const int64_t* __restrict__ ts, JoinGeom g,
@@ -758,20 +733,6 @@ __global__ void __launch_bounds__(kJoinThreads) k_join_filter(int64_t n, const i
     if (late) atomicAdd((ull*)&hdr[JH_LATE], (ull)late);
     if (flags) atomicOr((ull*)&hdr[JH_FLAGS], (ull)flags);
 }
-struct Cols3 {
-    const int64_t* in[3];
-    int64_t* out[3];
-};
-__global__ void __launch_bounds__(kJoinThreads) k_join_append(int64_t n, const uint32_t* __restrict__ keep,
-                                                              const uint32_t* __restrict__ off, Cols3 c) {
-    for (int64_t i = (int64_t)blockIdx.x * kJoinThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kJoinThreads) {
-        if (!keep[i]) continue;
-        const uint32_t d = off[i];
-        c.out[0][d] = c.in[0][i];
-        c.out[1][d] = c.in[1][i];
-        c.out[2][d] = c.in[2][i];
-    }
-}
 
 }  // namespace gw
 
@@ -781,13 +742,11 @@ using namespace gw;
 struct gw_join {
     gw_join_config cfg{};
     JoinGeom g{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    OpError er{kJoinName};
+    OpStream os;
     DevCols<3> log[2], alt, stage;
     int64_t n_log[2] = {0, 0};
-    DevCols<5> out;
-    DevBuf<uint8_t> pres;  // the rows' `present` bytes, row for row with `out`
-    int64_t out_from = 0, pending = 0;
+    RowBuf rows{true};  // the pending pairs; the byte column is the rows' `present`
     // gw_join_set_mode; `touched` once an ingest or a watermark has come
     int32_t mode = GW_JOIN_MODE_INNER;
     int64_t null_payload = 0;
@@ -799,52 +758,30 @@ struct gw_join {
     int64_t cg_n[3] = {0, 0, 0};  // groups, left elements, right elements
     DevBuf<char> scr;
     int64_t wm = INT64_MIN, late = 0, max_batch = 0;
-    bool failed = false;
-    std::string err;
     gw_join_stats st{};
 
-    int fail(int rc, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        if (rc != GW_E_OUTPUT_FULL && rc != GW_E_INVALID) failed = true;
-        return rc;
-    }
-    int dev_fail(hipError_t e) { return fail(GW_E_DEVICE, "window join: %s", hipGetErrorString(e)); }
-
-    // hdr, keep, off and the scan's block sums for n records
-    int filter_scratch(int64_t n, RecArrays& R) {
-        Carve sz{nullptr};
-        R.carve(sz, n);
-        if (scr.reserve_discard((int64_t)sz.at) != hipSuccess) return fail(GW_E_OOM, "window join: out of device memory");
-        Carve c{scr.p};
-        R.carve(c, n);
-        return GW_OK;
-    }
     // The records of (key, ts, pay)[0..n) with a window open at `w`, in order, to dst columns
-    // from row `at`; *kept and *dropped their numbers.  One synchronisation.
+    // from row `at`; *kept and *dropped their numbers.  One synchronisation, at its end, so the
+    // scratch (hdr, keep, off, the scan's block sums) is never in use when the next call grows it.
     int filter_into(int64_t n, const int64_t* key, const int64_t* ts, const int64_t* pay, int64_t w, int64_t* const* dst,
                     int64_t at, int64_t* kept, int64_t* dropped) {
+        hipStream_t stream = os.stream;
         RecArrays R;
-        int rc = filter_scratch(n, R);
+        int rc = carve_from([&](Carve& c) { R.carve(c, n); }, scr, er, nullptr);
         if (rc) return rc;
         hipLaunchKernelGGL(k_join_hdr_init, dim3(1), dim3(kJoinThreads), 0, stream, R.hdr);
         hipLaunchKernelGGL(k_join_filter, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, ts, g, w, R.cnt, R.hdr);
         hipError_t e = scan_excl<uint32_t, uint32_t>(R.cnt, R.toff, n, R.blk, R.hdr + JH_KEPT, stream);
-        if (e != hipSuccess) return dev_fail(e);
+        if (e != hipSuccess) return er.dev_fail(e);
         Cols3 c{{key, ts, pay}, {dst[0] + at, dst[1] + at, dst[2] + at}};
-        hipLaunchKernelGGL(k_join_append, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, R.cnt, R.toff, c);
+        hipLaunchKernelGGL(k_compact3, dim3(grid_for(n)), dim3(kJoinThreads), 0, stream, n, R.cnt, R.toff, c);
         int64_t h[kJoinHdr];
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, R.hdr, sizeof h, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return dev_fail(e);
+        if (e == hipSuccess) e = read_hdr(h, R.hdr, kJoinHdr, stream);
+        if (e != hipSuccess) return er.dev_fail(e);
         if (h[JH_FLAGS] & GW_DF_NO_TS)
-            return fail(GW_E_NO_TIMESTAMP, "Record has Long.MIN_VALUE timestamp (= no timestamp marker)");
-        if (h[JH_FLAGS] & GW_DF_RANGE) return fail(GW_E_RANGE, "window join: window bounds overflow int64");
+            return er.fail(GW_E_NO_TIMESTAMP, "Record has Long.MIN_VALUE timestamp (= no timestamp marker)");
+        if (h[JH_FLAGS] & GW_DF_RANGE) return er.fail(GW_E_RANGE, "window join: window bounds overflow int64");
         *kept = h[JH_KEPT];
         *dropped = h[JH_LATE];
         return GW_OK;
@@ -852,9 +789,9 @@ struct gw_join {
     int reserve_log(int side, int64_t need) {
         if (need <= log[side].cap) return GW_OK;
         const int64_t cap = std::max<int64_t>(need, 2 * log[side].cap);
-        if (log[side].reserve_keep(cap, 0, n_log[side], stream) != hipSuccess) {
+        if (log[side].reserve_keep(cap, 0, n_log[side], os.stream) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(GW_E_OOM, "window join: out of device memory growing the %s log", side ? "right" : "left");
+            return er.fail(GW_E_OOM, "window join: out of device memory growing the %s log", side ? "right" : "left");
         }
         ++st.log_growths;
         return GW_OK;
@@ -872,30 +809,19 @@ struct gw_join {
         }
         return GW_OK;
     }
-    int reserve_out(int64_t more) {
-        if (out_from + pending + more <= out.cap) return GW_OK;
-        const int64_t cap = std::max<int64_t>(pending + more, 2 * out.cap);
-        if (out.reserve_keep(cap, out_from, pending, stream) != hipSuccess ||
-            pres.reserve_keep(cap, out_from, pending, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GW_E_OOM, "window join: out of device memory for %lld pending pairs", (long long)(pending + more));
-        }
-        out_from = 0;
-        return GW_OK;
-    }
     // room for `more` groups and elements behind the pending CSR (the offsets: one row more)
     int reserve_cogroup(const int64_t more[3]) {
         hipError_t e = hipSuccess;
         const int64_t need_g = cg_n[0] + more[0] + 1;
-        if (need_g > cg.cap) e = cg.reserve_keep(std::max<int64_t>(need_g, 2 * cg.cap), 0, cg.cap ? cg_n[0] + 1 : 0, stream);
+        if (need_g > cg.cap) e = cg.reserve_keep(std::max<int64_t>(need_g, 2 * cg.cap), 0, cg.cap ? cg_n[0] + 1 : 0, os.stream);
         for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
             const int64_t need = cg_n[1 + sd] + more[1 + sd];
             if (need > cg_elem[sd].cap)
-                e = cg_elem[sd].reserve_keep(std::max<int64_t>(need, 2 * cg_elem[sd].cap), 0, cg_n[1 + sd], stream);
+                e = cg_elem[sd].reserve_keep(std::max<int64_t>(need, 2 * cg_elem[sd].cap), 0, cg_n[1 + sd], os.stream);
         }
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            return fail(GW_E_OOM, "window join: out of device memory for %lld pending groups", (long long)(cg_n[0] + more[0]));
+            return er.fail(GW_E_OOM, "window join: out of device memory for %lld pending groups", (long long)(cg_n[0] + more[0]));
         }
         return GW_OK;
     }
@@ -931,28 +857,30 @@ struct gw_join {
                     o = CoGroupOut{cg[0] + cg_n[0], cg[1] + cg_n[0], cg[2] + cg_n[0], cg[3] + cg_n[0], cg[4] + cg_n[0],
                                    cg_elem[0][0], cg_elem[1][0], cg_n[1], cg_n[2]};
                     return (int)GW_OK;
-                }, n3, &tuples, stream, why);
-                if (rc) return failed ? rc : fail(rc, "%s", why.c_str());
+                }, n3, &tuples, os.stream, why);
+                if (rc) return er.failed ? rc : er.fail(rc, "%s", why.c_str());
                 fired = n3[0];
                 for (int c = 0; c < 3; ++c) cg_n[c] += n3[c];
             } else {
                 rc = join_run(a, mode, null_payload, INT64_MAX / (mode ? 41 : 40), [&](int64_t total, JoinOut& o, std::string&) {
-                    int r = reserve_out(total);
-                    if (r) return r;
-                    for (int c = 0; c < 5; ++c) o.col[c] = out[c] + out_from + pending;
-                    o.present = pres.p + out_from + pending;
+                    if (rows.reserve(total, os.stream) != hipSuccess) {
+                        (void)hipGetLastError();
+                        return er.fail(GW_E_OOM, "window join: out of device memory for %lld pending pairs",
+                                       (long long)(rows.pending + total));
+                    }
+                    o.present = rows.tail(o.col);
                     return (int)GW_OK;
-                }, &fired, &tuples, stream, why);
-                if (rc) return failed ? rc : fail(rc, "%s", why.c_str());
-                pending += fired;
+                }, &fired, &tuples, os.stream, why);
+                if (rc) return er.failed ? rc : er.fail(rc, "%s", why.c_str());
+                rows.pending += fired;
             }
         }
         // the records whose last window has fired leave the logs
         for (int sd = 0; sd < 2; ++sd) {
             if (n_log[sd] == 0) continue;
-            if (alt.cap < n_log[sd] && alt.reserve_keep(std::max(n_log[sd], log[sd].cap), 0, 0, stream) != hipSuccess) {
+            if (alt.cap < n_log[sd] && alt.reserve_keep(std::max(n_log[sd], log[sd].cap), 0, 0, os.stream) != hipSuccess) {
                 (void)hipGetLastError();
-                return fail(GW_E_OOM, "window join: out of device memory compacting a log");
+                return er.fail(GW_E_OOM, "window join: out of device memory compacting a log");
             }
             int64_t kept = 0, dropped = 0;
             const int rc = filter_into(n_log[sd], log[sd][0], log[sd][1], log[sd][2], w, alt.col, 0, &kept, &dropped);
@@ -1026,12 +954,8 @@ static int join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts,
         set_last_error("window join: more than 2^31 - 1 records on one side");
         return GW_E_UNSUPPORTED;
     }
-    JoinTimes t;
-    if (expand_ms && (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess)) {
-        if (t.e0) (void)hipEventDestroy(t.e0);
-        set_last_error("window join: hipEventCreate");
-        return GW_E_DEVICE;
-    }
+    TimedPair t;
+    if (expand_ms && t.create() != hipSuccess) { set_last_error("window join: hipEventCreate"); return GW_E_DEVICE; }
     JoinIn a{{d_lkey, d_rkey}, {d_lts, d_rts}, {d_lpay, d_rpay}, n_l, n_l + n_r, g, w0, w1};
     int64_t pairs = 0;
     rc = join_run(a, mode, null_payload, max_rows, [&](int64_t total, JoinOut& o, std::string& w) {
@@ -1039,13 +963,9 @@ static int join_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_lts,
         if (total > cap) { w = "window join: output arrays too small"; return (int)GW_E_OUTPUT_FULL; }
         o = JoinOut{{d_key_out, d_start_out, d_end_out, d_lpay_out, d_rpay_out}, d_present_out, 0};
         return (int)GW_OK;
-    }, &pairs, nullptr, (hipStream_t)stream, why, expand_ms ? &t : nullptr);
-    if (expand_ms) {
-        float ms = 0;
-        if (rc == GW_OK && pairs > 0 && hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) *expand_ms = ms;
-        (void)hipEventDestroy(t.e0);
-        (void)hipEventDestroy(t.e1);
-    }
+    }, &pairs, nullptr, (hipStream_t)stream, why, t);
+    float ms = 0;
+    if (expand_ms && rc == GW_OK && pairs > 0 && t.elapsed(&ms) == hipSuccess) *expand_ms = ms;
     if (rc) set_last_error(why);
     return rc;
 }
@@ -1116,12 +1036,8 @@ static int cogroup_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_l
         return (int)GW_OK;
     };
     if (n_l + n_r == 0 || w1 <= w0) return no_groups();
-    JoinTimes t;
-    if (write_ms && (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess)) {
-        if (t.e0) (void)hipEventDestroy(t.e0);
-        set_last_error("window coGroup: hipEventCreate");
-        return GW_E_DEVICE;
-    }
+    TimedPair t;
+    if (write_ms && t.create() != hipSuccess) { set_last_error("window coGroup: hipEventCreate"); return GW_E_DEVICE; }
     JoinIn a{{d_lkey, d_rkey}, {d_lts, d_rts}, {d_lpay, d_rpay}, n_l, n_l + n_r, g, w0, w1};
     bool wrote = false;
     rc = cogroup_run(a, [&](int64_t ng, int64_t nl, int64_t nr, CoGroupOut& o, std::string& w) {
@@ -1134,13 +1050,9 @@ static int cogroup_device(int64_t n_l, const int64_t* d_lkey, const int64_t* d_l
         o = CoGroupOut{d_key_out, d_start_out, d_end_out, d_loff_out, d_roff_out, d_lelem_out, d_relem_out, 0, 0};
         wrote = true;
         return (int)GW_OK;
-    }, n_out, nullptr, s, why, write_ms ? &t : nullptr);
-    if (write_ms) {
-        float ms = 0;
-        if (rc == GW_OK && wrote && hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) *write_ms = ms;
-        (void)hipEventDestroy(t.e0);
-        (void)hipEventDestroy(t.e1);
-    }
+    }, n_out, nullptr, s, why, t);
+    float ms = 0;
+    if (write_ms && rc == GW_OK && wrote && t.elapsed(&ms) == hipSuccess) *write_ms = ms;
     if (rc) set_last_error(why);
     return rc;
 }
@@ -1395,98 +1307,63 @@ int gw_join_create(const gw_join_config* cfg, gw_join** out) {
     h->cfg = *cfg;
     h->g = g;
     h->max_batch = cfg->max_batch > 0 ? std::min<int64_t>(cfg->max_batch, (int64_t)1 << 30) : (int64_t)1 << 22;
-    hipError_t e = hipSetDevice(cfg->device);
-    if (e != hipSuccess) return bail(GW_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail(GW_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-    if ((e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming)) != hipSuccess)
-        return bail(GW_E_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    const char* what;
+    const hipError_t e = h->os.create(cfg->device, &what);
+    if (e != hipSuccess) return bail(GW_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
     const int64_t cap0 = std::max<int64_t>(cfg->capacity_hint, 16);
     for (int sd = 0; sd < 2; ++sd)
-        if (h->log[sd].reserve_keep(cap0, 0, 0, h->stream) != hipSuccess) return bail(GW_E_OOM, "window join: out of device memory");
+        if (h->log[sd].reserve_keep(cap0, 0, 0, h->os.stream) != hipSuccess) return bail(GW_E_OOM, "window join: out of device memory");
     *out = h;
     return GW_OK;
 }
 
 int gw_join_destroy(gw_join* h) {
     if (!h) return GW_OK;
-    hipSetDevice(h->cfg.device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->ev_in) hipEventDestroy(h->ev_in);
-    if (h->ev_out) hipEventDestroy(h->ev_out);
-    if (h->stream) hipStreamDestroy(h->stream);
+    h->os.destroy();
     delete h;
     return GW_OK;
 }
 
-const char* gw_join_last_error(const gw_join* h) { return h ? h->err.c_str() : gw_last_error(nullptr); }
-
-#define JOIN_ENTER(h)                                                                     \
-    if (!(h)) return GW_E_INVALID;                                                        \
-    if ((h)->failed) return GW_E_STATE;                                                   \
-    hipSetDevice((h)->cfg.device)
+const char* gw_join_last_error(const gw_join* h) { return h ? h->er.err.c_str() : gw_last_error(nullptr); }
 
 int gw_join_ingest_device(gw_join* h, int32_t side, int64_t n, const int64_t* d_key, const int64_t* d_ts,
                           const int64_t* d_payload, void* stream) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     if ((side != 0 && side != 1) || n < 0 || (n > 0 && (!d_key || !d_ts || !d_payload)))
-        return h->fail(GW_E_INVALID, "gw_join_ingest_device: bad side or null column");
+        return h->er.fail(GW_E_INVALID, "gw_join_ingest_device: bad side or null column");
     h->touched = true;
-    if (n + h->n_log[side] > INT32_MAX) return h->fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
-    hipStream_t ps = (hipStream_t)stream;
-    if (ps != h->stream) {
-        hipEventRecord(h->ev_in, ps);
-        hipStreamWaitEvent(h->stream, h->ev_in, 0);
-    }
-    if (n == 0) return GW_OK;
-    const int rc = h->ingest_cols(side, n, d_key, d_ts, d_payload);
-    if (ps != h->stream) {
-        hipEventRecord(h->ev_out, h->stream);
-        hipStreamWaitEvent(ps, h->ev_out, 0);
-    }
-    return rc;
+    if (n + h->n_log[side] > INT32_MAX) return h->er.fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
+    OpStream::Handoff handoff(h->os, (hipStream_t)stream, n > 0);
+    return h->ingest_cols(side, n, d_key, d_ts, d_payload);
 }
 
 int gw_join_ingest(gw_join* h, int32_t side, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* payload) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     if ((side != 0 && side != 1) || n < 0 || (n > 0 && (!key || !ts || !payload)))
-        return h->fail(GW_E_INVALID, "gw_join_ingest: bad side or null column");
+        return h->er.fail(GW_E_INVALID, "gw_join_ingest: bad side or null column");
     h->touched = true;
-    if (n + h->n_log[side] > INT32_MAX) return h->fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
-    for (int64_t at = 0; at < n; at += h->max_batch) {
-        const int64_t m = std::min(h->max_batch, n - at);
-        if (h->stage.cap < m && h->stage.reserve_keep(m, 0, 0, h->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return h->fail(GW_E_OOM, "window join: out of device memory staging a batch");
-        }
-        const int64_t* src[3] = {key + at, ts + at, payload + at};
-        for (int c = 0; c < 3; ++c) {
-            const hipError_t e = hipMemcpyAsync(h->stage[c], src[c], (size_t)m * 8, hipMemcpyHostToDevice, h->stream);
-            if (e != hipSuccess) return h->dev_fail(e);
-        }
-        // (ingest_cols waits for the stream, so the host columns are free when this returns)
-        const int rc = h->ingest_cols(side, m, h->stage[0], h->stage[1], h->stage[2]);
-        if (rc) return rc;
-    }
-    return GW_OK;
+    if (n + h->n_log[side] > INT32_MAX) return h->er.fail(GW_E_UNSUPPORTED, "window join: more than 2^31 - 1 live records on one side");
+    const int64_t* src[3] = {key, ts, payload};
+    // (ingest_cols waits for the stream, so the host columns are free when this returns)
+    return staged_ingest(h->stage, h->max_batch, n, src, h->os.stream, h->er,
+                         [&](int64_t m, int64_t* const* d) { return h->ingest_cols(side, m, d[0], d[1], d[2]); });
 }
 
 int gw_join_advance_watermark(gw_join* h, int64_t watermark, int64_t* pairs_fired) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     return h->advance(watermark, pairs_fired);
 }
 
 int gw_join_end_input(gw_join* h, int64_t* pairs_fired) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     return h->advance(INT64_MAX, pairs_fired);
 }
 
 int gw_join_set_mode(gw_join* h, int32_t mode, int64_t null_payload) {
-    JOIN_ENTER(h);
-    if (mode < GW_JOIN_MODE_INNER || mode > GW_JOIN_MODE_COGROUP) return h->fail(GW_E_INVALID, "gw_join_set_mode: unknown mode");
+    GW_OP_ENTER(h);
+    if (mode < GW_JOIN_MODE_INNER || mode > GW_JOIN_MODE_COGROUP) return h->er.fail(GW_E_INVALID, "gw_join_set_mode: unknown mode");
     if (h->touched) {  // (not a failure of the handle: it goes on in the mode it has)
-        h->err = "gw_join_set_mode: only before the first ingest or watermark";
+        h->er.err = "gw_join_set_mode: only before the first ingest or watermark";
         return GW_E_STATE;
     }
     h->mode = mode;
@@ -1495,38 +1372,26 @@ int gw_join_set_mode(gw_join* h, int32_t mode, int64_t null_payload) {
 }
 
 #define JOIN_PAIRS(h, what)                                                                          \
-    if ((h)->mode == GW_JOIN_MODE_COGROUP) return (h)->fail(GW_E_INVALID, what ": the handle is in coGroup mode")
+    if ((h)->mode == GW_JOIN_MODE_COGROUP) return (h)->er.fail(GW_E_INVALID, what ": the handle is in coGroup mode")
 #define JOIN_COGROUP(h, what)                                                                        \
-    if ((h)->mode != GW_JOIN_MODE_COGROUP) return (h)->fail(GW_E_INVALID, what ": the handle is not in coGroup mode")
+    if ((h)->mode != GW_JOIN_MODE_COGROUP) return (h)->er.fail(GW_E_INVALID, what ": the handle is not in coGroup mode")
 
 int gw_join_pending(gw_join* h, int64_t* n) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     JOIN_PAIRS(h, "gw_join_pending");
-    if (!n) return h->fail(GW_E_INVALID, "gw_join_pending: null argument");
-    *n = h->pending;
+    if (!n) return h->er.fail(GW_E_INVALID, "gw_join_pending: null argument");
+    *n = h->rows.pending;
     return GW_OK;
 }
 
 int gw_join_drain_outer(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay,
                         uint8_t* present, int64_t cap, int64_t* n) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     JOIN_PAIRS(h, "gw_join_drain");
     if (!n || cap < 0 || (cap > 0 && (!key || !start || !end || !lpay || !rpay)))
-        return h->fail(GW_E_INVALID, "gw_join_drain: bad argument");
-    const int64_t m = std::min(cap, h->pending);
-    *n = m;
-    int64_t* dst[5] = {key, start, end, lpay, rpay};
-    hipError_t e = hipSuccess;
-    for (int c = 0; c < 5 && m > 0 && e == hipSuccess; ++c)
-        e = hipMemcpyAsync(dst[c], h->out[c] + h->out_from, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream);
-    if (present && m > 0 && e == hipSuccess)
-        e = hipMemcpyAsync(present, h->pres.p + h->out_from, (size_t)m, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return h->dev_fail(e);
-    h->out_from += m;
-    h->pending -= m;
-    if (h->pending == 0) h->out_from = 0;
-    return h->pending > 0 ? GW_E_OUTPUT_FULL : GW_OK;
+        return h->er.fail(GW_E_INVALID, "gw_join_drain: bad argument");
+    int64_t* const dst[5] = {key, start, end, lpay, rpay};
+    return h->rows.drain(dst, present, cap, n, h->os.stream, h->er);
 }
 
 int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* lpay, int64_t* rpay, int64_t cap,
@@ -1536,13 +1401,11 @@ int gw_join_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_
 
 int gw_join_rows_device_outer(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
                               const int64_t** d_lpay, const int64_t** d_rpay, const uint8_t** d_present, int64_t* n) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     JOIN_PAIRS(h, "gw_join_rows_device");
-    if (!d_key || !d_start || !d_end || !d_lpay || !d_rpay || !n) return h->fail(GW_E_INVALID, "gw_join_rows_device: null argument");
-    const int64_t** dst[5] = {d_key, d_start, d_end, d_lpay, d_rpay};
-    for (int c = 0; c < 5; ++c) *dst[c] = h->pending ? h->out[c] + h->out_from : nullptr;
-    if (d_present) *d_present = h->pending ? h->pres.p + h->out_from : nullptr;
-    *n = h->pending;
+    if (!d_key || !d_start || !d_end || !d_lpay || !d_rpay || !n) return h->er.fail(GW_E_INVALID, "gw_join_rows_device: null argument");
+    const int64_t** const dst[5] = {d_key, d_start, d_end, d_lpay, d_rpay};
+    h->rows.view(dst, d_present, n);
     return GW_OK;
 }
 
@@ -1552,9 +1415,9 @@ int gw_join_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_sta
 }
 
 int gw_join_cogroup_pending(gw_join* h, int64_t* n) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     JOIN_COGROUP(h, "gw_join_cogroup_pending");
-    if (!n) return h->fail(GW_E_INVALID, "gw_join_cogroup_pending: null argument");
+    if (!n) return h->er.fail(GW_E_INVALID, "gw_join_cogroup_pending: null argument");
     for (int c = 0; c < 3; ++c) n[c] = h->cg_n[c];
     return GW_OK;
 }
@@ -1562,25 +1425,25 @@ int gw_join_cogroup_pending(gw_join* h, int64_t* n) {
 int gw_join_cogroup_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end, int64_t* loff, int64_t* roff,
                           int64_t* lelem, int64_t cap_left, int64_t* relem, int64_t cap_right, int64_t cap_groups,
                           int64_t* n) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     JOIN_COGROUP(h, "gw_join_cogroup_drain");
     const int64_t* m = h->cg_n;
     if (!n || cap_groups < 0 || cap_left < 0 || cap_right < 0 || !loff || !roff ||
         (cap_groups > 0 && (!key || !start || !end)) || (cap_left > 0 && !lelem) || (cap_right > 0 && !relem))
-        return h->fail(GW_E_INVALID, "gw_join_cogroup_drain: bad argument");
+        return h->er.fail(GW_E_INVALID, "gw_join_cogroup_drain: bad argument");
     for (int c = 0; c < 3; ++c) n[c] = m[c];
     if (m[0] > cap_groups || m[1] > cap_left || m[2] > cap_right)
-        return h->fail(GW_E_OUTPUT_FULL, "gw_join_cogroup_drain: output arrays too small");
+        return h->er.fail(GW_E_OUTPUT_FULL, "gw_join_cogroup_drain: output arrays too small");
     loff[0] = roff[0] = 0;
     if (m[0] == 0) return GW_OK;
     int64_t* dst[5] = {key, start, end, loff, roff};
     hipError_t e = hipSuccess;
     for (int c = 0; c < 5 && e == hipSuccess; ++c)
-        e = hipMemcpyAsync(dst[c], h->cg[c], (size_t)(m[0] + (c >= 3)) * 8, hipMemcpyDeviceToHost, h->stream);
-    if (m[1] > 0 && e == hipSuccess) e = hipMemcpyAsync(lelem, h->cg_elem[0][0], (size_t)m[1] * 8, hipMemcpyDeviceToHost, h->stream);
-    if (m[2] > 0 && e == hipSuccess) e = hipMemcpyAsync(relem, h->cg_elem[1][0], (size_t)m[2] * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return h->dev_fail(e);
+        e = hipMemcpyAsync(dst[c], h->cg[c], (size_t)(m[0] + (c >= 3)) * 8, hipMemcpyDeviceToHost, h->os.stream);
+    if (m[1] > 0 && e == hipSuccess) e = hipMemcpyAsync(lelem, h->cg_elem[0][0], (size_t)m[1] * 8, hipMemcpyDeviceToHost, h->os.stream);
+    if (m[2] > 0 && e == hipSuccess) e = hipMemcpyAsync(relem, h->cg_elem[1][0], (size_t)m[2] * 8, hipMemcpyDeviceToHost, h->os.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->os.stream);
+    if (e != hipSuccess) return h->er.dev_fail(e);
     h->cg_n[0] = h->cg_n[1] = h->cg_n[2] = 0;
     return GW_OK;
 }
@@ -1588,10 +1451,10 @@ int gw_join_cogroup_drain(gw_join* h, int64_t* key, int64_t* start, int64_t* end
 int gw_join_cogroup_rows_device(gw_join* h, const int64_t** d_key, const int64_t** d_start, const int64_t** d_end,
                                 const int64_t** d_loff, const int64_t** d_roff, const int64_t** d_lelem,
                                 const int64_t** d_relem, int64_t* n) {
-    JOIN_ENTER(h);
+    GW_OP_ENTER(h);
     JOIN_COGROUP(h, "gw_join_cogroup_rows_device");
     if (!d_key || !d_start || !d_end || !d_loff || !d_roff || !d_lelem || !d_relem || !n)
-        return h->fail(GW_E_INVALID, "gw_join_cogroup_rows_device: null argument");
+        return h->er.fail(GW_E_INVALID, "gw_join_cogroup_rows_device: null argument");
     const int64_t** dst[5] = {d_key, d_start, d_end, d_loff, d_roff};
     for (int c = 0; c < 5; ++c) *dst[c] = h->cg_n[0] ? h->cg[c] : nullptr;
     *d_lelem = h->cg_n[1] ? h->cg_elem[0][0] : nullptr;
@@ -1601,9 +1464,8 @@ int gw_join_cogroup_rows_device(gw_join* h, const int64_t** d_key, const int64_t
 }
 
 int gw_join_clear_rows(gw_join* h) {
-    JOIN_ENTER(h);
-    h->pending = 0;
-    h->out_from = 0;
+    GW_OP_ENTER(h);
+    h->rows.clear();
     h->cg_n[0] = h->cg_n[1] = h->cg_n[2] = 0;
     return GW_OK;
 }
@@ -1620,6 +1482,6 @@ int gw_join_get_stats(const gw_join* h, gw_join_stats* out) {
     return GW_OK;
 }
 
-void* gw_join_stream(gw_join* h) { return h ? (void*)h->stream : nullptr; }
+void* gw_join_stream(gw_join* h) { return h ? (void*)h->os.stream : nullptr; }
 
 }  // extern "C"

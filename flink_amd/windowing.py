@@ -1324,51 +1324,29 @@ class GpuWindowOperator:
 
 
 # -------------------------------------------------------------- DataStream surface
-class GpuWindowJoinOperator:
-    """Event-time window join of two keyed streams on one MI355X (gw_join): Flink's
-    stream.join(other).where().equalTo().window(assigner).apply(), i.e. union -> keyBy ->
-    WindowOperator with ListState -> JoinCoGroupFunction.  Records are (key, ts, payload) int64
-    columns per side (payload: the element as the caller numbers or packs it); a fire leaves
-    (key, start, end, left payload, right payload) pairs, windows by ascending end, keys ascending,
-    left-major in arrival order.  Tumbling and sliding event-time windows, allowed lateness 0.
-    mode: "inner" (default), "left_outer", "right_outer", "full_outer" -- the unmatched records of
-    the kept sides come as rows with null_payload in the lacking column, drain_outer() adds the
-    present column -- or "cogroup": a fire leaves the groups themselves, one-sided ones included,
-    as a CSR (cogroup_drain, cogroup_rows_device)."""
+class _TwoStreamOperator:
+    """What the two-stream operators share around their C handles, whose entry points differ only
+    in the prefix (gw_join_*, gw_ijoin_*): the handle's life, the error check, ingest of host and
+    device columns, and the pending rows (five int64 columns; drain, view, clear).  A subclass
+    sets _prefix and _stats_type and builds self.cfg."""
 
-    LEFT, RIGHT = N.JOIN_LEFT, N.JOIN_RIGHT
+    _prefix, _stats_type = "", None
 
-    def __init__(self, assigner: WindowAssigner, device: int = 0, capacity_hint: int = 0, max_batch: int = 0,
-                 mode="inner", null_payload: int = 0):
-        self.assigner = assigner
-        self.mode = _join_mode(mode, cogroup_ok=True)
-        self.null_payload = int(null_payload)
-        c = N.GwJoinConfig()
-        c.assigner, c.size, c.slide, c.offset = _join_geometry(assigner)
-        c.device, c.capacity_hint, c.max_batch = device, capacity_hint, max_batch
-        self.cfg = c
-        self._h = None
+    def _fn(self, name: str):
+        return getattr(N.lib(), f"{self._prefix}_{name}")
 
     def open(self):
         h = ctypes.c_void_p()
-        rc = N.lib().gw_join_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        rc = self._fn("create")(ctypes.byref(self.cfg), ctypes.byref(h))
         if rc == N.GW_E_INVALID:
             raise ValueError(N.lib().gw_last_error(None).decode())
         N.check(rc, None)
         self._h = h
-        if self.mode != N.JOIN_MODE_INNER:
-            self.set_mode(self.mode, self.null_payload)
         return self
-
-    def set_mode(self, mode, null_payload: int = 0):
-        """gw_join_set_mode: only before the first batch or watermark (GW_E_STATE afterwards)."""
-        m = _join_mode(mode, cogroup_ok=True)
-        self._check(N.lib().gw_join_set_mode(self._h, m, int(null_payload)))
-        self.mode, self.null_payload = m, int(null_payload)
 
     def close(self):
         if self._h:
-            N.lib().gw_join_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -1385,28 +1363,120 @@ class GpuWindowJoinOperator:
 
     def _check(self, rc: int):
         if rc != N.GW_OK:
-            msg = N.lib().gw_join_last_error(self._h)
+            msg = self._fn("last_error")(self._h)
             raise N.GpuWinError(rc, msg.decode() if msg else "")
         return rc
 
-    def process_batch(self, side: int, keys, ts, payload):
+    def _ingest(self, side: int, keys, ts, payload, *extra):
         keys, ts, payload = (np.ascontiguousarray(x, dtype=np.int64) for x in (keys, ts, payload))
         if not (len(keys) == len(ts) == len(payload)):
             raise ValueError("column lengths differ")
-        self._check(N.lib().gw_join_ingest(self._h, int(side), len(keys), _ptr(keys), _ptr(ts), _ptr(payload)))
+        self._check(self._fn("ingest")(self._h, int(side), len(keys), _ptr(keys), _ptr(ts), _ptr(payload), *extra))
 
-    def process_batch_device(self, side: int, keys, ts, payload, stream=None):
-        """Columns already in HBM (torch int64 tensors), produced on `stream` (default: torch's
-        current): the operator reads them behind that stream's work, and the stream waits for
-        the reads."""
+    def _ingest_device(self, side: int, keys, ts, payload, stream, *extra):
         if not (keys.numel() == ts.numel() == payload.numel()):
             raise ValueError("column lengths differ")
         if stream is None:
             import torch
             stream = torch.cuda.current_stream(keys.device).cuda_stream
         P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
-        self._check(N.lib().gw_join_ingest_device(self._h, int(side), keys.numel(), P(keys), P(ts), P(payload),
-                                                  ctypes.c_void_p(stream) if stream else None))
+        self._check(self._fn("ingest_device")(self._h, int(side), keys.numel(), P(keys), P(ts), P(payload),
+                                              ctypes.c_void_p(stream) if stream else None, *extra))
+
+    def pending(self) -> int:
+        n = ctypes.c_int64(0)
+        self._check(self._fn("pending")(self._h, ctypes.byref(n)))
+        return n.value
+
+    def _drain(self, fn, byte_column: bool, cap: Optional[int]):
+        """All pending rows through fn (a drain entry point), cap rows per call (default: all at
+        once): five int64 numpy columns, and a uint8 one behind them where fn takes one."""
+        n = self.pending()
+        out = [np.empty(n, np.int64) for _ in range(5)]
+        if byte_column:
+            out.append(np.empty(n, np.uint8))
+        step = n if cap is None else max(1, int(cap))
+        at = 0
+        got = ctypes.c_int64(0)
+        while at < n:
+            rc = fn(self._h, *[ctypes.c_void_p(o.ctypes.data + o.itemsize * at) for o in out], step, ctypes.byref(got))
+            if rc != N.GW_E_OUTPUT_FULL:
+                self._check(rc)
+            at += got.value
+            if rc == N.GW_OK:
+                break
+        assert at == n
+        return tuple(out)
+
+    def rows_device(self):
+        """Zero-copy view of the pending rows: five device pointers and their number."""
+        p = [ctypes.c_void_p() for _ in range(5)]
+        n = ctypes.c_int64(0)
+        self._check(self._fn("rows_device")(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
+        return [x.value for x in p], n.value
+
+    def clear_rows(self):
+        self._check(self._fn("clear_rows")(self._h))
+
+    def num_late_records_dropped(self) -> int:
+        return int(self._fn("late_dropped")(self._h))
+
+    def stats(self) -> dict:
+        s = self._stats_type()
+        self._fn("get_stats")(self._h, ctypes.byref(s))
+        return s.as_dict()
+
+    @property
+    def stream(self) -> int:
+        return self._fn("stream")(self._h) or 0
+
+
+class GpuWindowJoinOperator(_TwoStreamOperator):
+    """Event-time window join of two keyed streams on one MI355X (gw_join): Flink's
+    stream.join(other).where().equalTo().window(assigner).apply(), i.e. union -> keyBy ->
+    WindowOperator with ListState -> JoinCoGroupFunction.  Records are (key, ts, payload) int64
+    columns per side (payload: the element as the caller numbers or packs it); a fire leaves
+    (key, start, end, left payload, right payload) pairs, windows by ascending end, keys ascending,
+    left-major in arrival order.  Tumbling and sliding event-time windows, allowed lateness 0.
+    mode: "inner" (default), "left_outer", "right_outer", "full_outer" -- the unmatched records of
+    the kept sides come as rows with null_payload in the lacking column, drain_outer() adds the
+    present column -- or "cogroup": a fire leaves the groups themselves, one-sided ones included,
+    as a CSR (cogroup_drain, cogroup_rows_device)."""
+
+    LEFT, RIGHT = N.JOIN_LEFT, N.JOIN_RIGHT
+    _prefix, _stats_type = "gw_join", N.GwJoinStats
+
+    def __init__(self, assigner: WindowAssigner, device: int = 0, capacity_hint: int = 0, max_batch: int = 0,
+                 mode="inner", null_payload: int = 0):
+        self.assigner = assigner
+        self.mode = _join_mode(mode, cogroup_ok=True)
+        self.null_payload = int(null_payload)
+        c = N.GwJoinConfig()
+        c.assigner, c.size, c.slide, c.offset = _join_geometry(assigner)
+        c.device, c.capacity_hint, c.max_batch = device, capacity_hint, max_batch
+        self.cfg = c
+        self._h = None
+
+    def open(self):
+        super().open()
+        if self.mode != N.JOIN_MODE_INNER:
+            self.set_mode(self.mode, self.null_payload)
+        return self
+
+    def set_mode(self, mode, null_payload: int = 0):
+        """gw_join_set_mode: only before the first batch or watermark (GW_E_STATE afterwards)."""
+        m = _join_mode(mode, cogroup_ok=True)
+        self._check(N.lib().gw_join_set_mode(self._h, m, int(null_payload)))
+        self.mode, self.null_payload = m, int(null_payload)
+
+    def process_batch(self, side: int, keys, ts, payload):
+        self._ingest(side, keys, ts, payload)
+
+    def process_batch_device(self, side: int, keys, ts, payload, stream=None):
+        """Columns already in HBM (torch int64 tensors), produced on `stream` (default: torch's
+        current): the operator reads them behind that stream's work, and the stream waits for
+        the reads."""
+        self._ingest_device(side, keys, ts, payload, stream)
 
     def advance_watermark(self, wm: int) -> int:
         fired = ctypes.c_int64(0)
@@ -1418,55 +1488,14 @@ class GpuWindowJoinOperator:
         self._check(N.lib().gw_join_end_input(self._h, ctypes.byref(fired)))
         return fired.value
 
-    def pending(self) -> int:
-        n = ctypes.c_int64(0)
-        self._check(N.lib().gw_join_pending(self._h, ctypes.byref(n)))
-        return n.value
-
     def drain(self, cap: Optional[int] = None):
         """All pending pairs as numpy (key, start, end, left payload, right payload), copied cap
         pairs per call (default: all at once)."""
-        n = self.pending()
-        out = [np.empty(n, np.int64) for _ in range(5)]
-        step = n if cap is None else max(1, int(cap))
-        at = 0
-        got = ctypes.c_int64(0)
-        while at < n:
-            rc = N.lib().gw_join_drain(self._h, *[ctypes.c_void_p(o.ctypes.data + 8 * at) for o in out], step,
-                                       ctypes.byref(got))
-            if rc != N.GW_E_OUTPUT_FULL:
-                self._check(rc)
-            at += got.value
-            if rc == N.GW_OK:
-                break
-        assert at == n
-        return tuple(out)
+        return self._drain(N.lib().gw_join_drain, False, cap)
 
     def drain_outer(self, cap: Optional[int] = None):
         """drain() with the present column (uint8: 1 left only, 2 right only, 3 both) as a sixth."""
-        n = self.pending()
-        out = [np.empty(n, np.int64) for _ in range(5)]
-        pres = np.empty(n, np.uint8)
-        step = n if cap is None else max(1, int(cap))
-        at = 0
-        got = ctypes.c_int64(0)
-        while at < n:
-            rc = N.lib().gw_join_drain_outer(self._h, *[ctypes.c_void_p(o.ctypes.data + 8 * at) for o in out],
-                                             ctypes.c_void_p(pres.ctypes.data + at), step, ctypes.byref(got))
-            if rc != N.GW_E_OUTPUT_FULL:
-                self._check(rc)
-            at += got.value
-            if rc == N.GW_OK:
-                break
-        assert at == n
-        return tuple(out) + (pres,)
-
-    def rows_device(self):
-        """Zero-copy view of the pending pairs: five device pointers and their number."""
-        p = [ctypes.c_void_p() for _ in range(5)]
-        n = ctypes.c_int64(0)
-        self._check(N.lib().gw_join_rows_device(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
-        return [x.value for x in p], n.value
+        return self._drain(N.lib().gw_join_drain_outer, True, cap)
 
     def rows_device_outer(self):
         """rows_device() with the present column's pointer as a sixth."""
@@ -1498,21 +1527,6 @@ class GpuWindowJoinOperator:
         n = (ctypes.c_int64 * 3)()
         self._check(N.lib().gw_join_cogroup_rows_device(self._h, *[ctypes.byref(x) for x in p], n))
         return [x.value for x in p], tuple(n)
-
-    def clear_rows(self):
-        self._check(N.lib().gw_join_clear_rows(self._h))
-
-    def num_late_records_dropped(self) -> int:
-        return int(N.lib().gw_join_late_dropped(self._h))
-
-    def stats(self) -> dict:
-        s = N.GwJoinStats()
-        N.lib().gw_join_get_stats(self._h, ctypes.byref(s))
-        return s.as_dict()
-
-    @property
-    def stream(self) -> int:
-        return N.lib().gw_join_stream(self._h) or 0
 
 
 class JoinedStreams:
@@ -1640,7 +1654,7 @@ class CoGroupedStreams(JoinedStreams):
         return out
 
 
-class GpuIntervalJoinOperator:
+class GpuIntervalJoinOperator(_TwoStreamOperator):
     """Event-time interval join of two keyed streams on one MI355X (gw_ijoin): Flink's
     keyedA.intervalJoin(keyedB).between(lower, upper).process(), i.e. IntervalJoinOperator.  A left
     l and a right r pair when l.key == r.key and l.ts + lower <= r.ts <= l.ts + upper (inclusive).
@@ -1651,6 +1665,7 @@ class GpuIntervalJoinOperator:
     batches and removes the buffered records whose cleanup time has passed."""
 
     LEFT, RIGHT = N.JOIN_LEFT, N.JOIN_RIGHT
+    _prefix, _stats_type = "gw_ijoin", N.GwIJoinStats
 
     def __init__(self, lower: int, upper: int, device: int = 0, capacity_hint: int = 0, max_batch: int = 0):
         lower, upper = int(lower), int(upper)
@@ -1664,60 +1679,17 @@ class GpuIntervalJoinOperator:
         self.cfg = c
         self._h = None
 
-    def open(self):
-        h = ctypes.c_void_p()
-        rc = N.lib().gw_ijoin_create(ctypes.byref(self.cfg), ctypes.byref(h))
-        if rc == N.GW_E_INVALID:
-            raise ValueError(N.lib().gw_last_error(None).decode())
-        N.check(rc, None)
-        self._h = h
-        return self
-
-    def close(self):
-        if self._h:
-            N.lib().gw_ijoin_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self.open() if self._h is None else self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc != N.GW_OK:
-            msg = N.lib().gw_ijoin_last_error(self._h)
-            raise N.GpuWinError(rc, msg.decode() if msg else "")
-        return rc
-
     def process_batch(self, side: int, keys, ts, payload) -> int:
-        keys, ts, payload = (np.ascontiguousarray(x, dtype=np.int64) for x in (keys, ts, payload))
-        if not (len(keys) == len(ts) == len(payload)):
-            raise ValueError("column lengths differ")
         rows = ctypes.c_int64(0)
-        self._check(N.lib().gw_ijoin_ingest(self._h, int(side), len(keys), _ptr(keys), _ptr(ts), _ptr(payload),
-                                            ctypes.byref(rows)))
+        self._ingest(side, keys, ts, payload, ctypes.byref(rows))
         return rows.value
 
     def process_batch_device(self, side: int, keys, ts, payload, stream=None) -> int:
         """Columns already in HBM (torch int64 tensors), produced on `stream` (default: torch's
         current): the operator reads them behind that stream's work, and the stream waits for
         the reads."""
-        if not (keys.numel() == ts.numel() == payload.numel()):
-            raise ValueError("column lengths differ")
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(keys.device).cuda_stream
-        P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
         rows = ctypes.c_int64(0)
-        self._check(N.lib().gw_ijoin_ingest_device(self._h, int(side), keys.numel(), P(keys), P(ts), P(payload),
-                                                   ctypes.c_void_p(stream) if stream else None, ctypes.byref(rows)))
+        self._ingest_device(side, keys, ts, payload, stream, ctypes.byref(rows))
         return rows.value
 
     def advance_watermark(self, wm: int):
@@ -1726,57 +1698,16 @@ class GpuIntervalJoinOperator:
     def end_input(self):
         self._check(N.lib().gw_ijoin_end_input(self._h))
 
-    def pending(self) -> int:
-        n = ctypes.c_int64(0)
-        self._check(N.lib().gw_ijoin_pending(self._h, ctypes.byref(n)))
-        return n.value
-
     def drain(self, cap: Optional[int] = None):
         """All pending rows as numpy (key, left ts, right ts, left payload, right payload), copied
         cap rows per call (default: all at once)."""
-        n = self.pending()
-        out = [np.empty(n, np.int64) for _ in range(5)]
-        step = n if cap is None else max(1, int(cap))
-        at = 0
-        got = ctypes.c_int64(0)
-        while at < n:
-            rc = N.lib().gw_ijoin_drain(self._h, *[ctypes.c_void_p(o.ctypes.data + 8 * at) for o in out], step,
-                                        ctypes.byref(got))
-            if rc != N.GW_E_OUTPUT_FULL:
-                self._check(rc)
-            at += got.value
-            if rc == N.GW_OK:
-                break
-        assert at == n
-        return tuple(out)
-
-    def rows_device(self):
-        """Zero-copy view of the pending rows: five device pointers and their number."""
-        p = [ctypes.c_void_p() for _ in range(5)]
-        n = ctypes.c_int64(0)
-        self._check(N.lib().gw_ijoin_rows_device(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(n)))
-        return [x.value for x in p], n.value
-
-    def clear_rows(self):
-        self._check(N.lib().gw_ijoin_clear_rows(self._h))
-
-    def num_late_records_dropped(self) -> int:
-        return int(N.lib().gw_ijoin_late_dropped(self._h))
-
-    def stats(self) -> dict:
-        s = N.GwIJoinStats()
-        N.lib().gw_ijoin_get_stats(self._h, ctypes.byref(s))
-        return s.as_dict()
+        return self._drain(N.lib().gw_ijoin_drain, False, cap)
 
     def last_times(self):
         """(probe stage ms, merge ms) of the last ingest pass on the device; waits for the stream."""
         a, b = ctypes.c_double(0), ctypes.c_double(0)
         self._check(N.lib().gw_ijoin_last_times(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
-
-    @property
-    def stream(self) -> int:
-        return N.lib().gw_ijoin_stream(self._h) or 0
 
 
 @dataclass

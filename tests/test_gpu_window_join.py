@@ -242,6 +242,40 @@ def test_operator_matches_reference(seed, geometry, device_ingest):
         side_stream.synchronize()
 
 
+def test_empty_device_batch_on_a_side_stream_between_two_batches():
+    """process_batch_device with no records on a producer stream that is not the operator's: the
+    operator launches nothing, and the batches before and after it join as if it had not come."""
+    size, slide, offset = GEOMETRIES["sliding"]
+    sides = _streams(3, "sliding")
+    ref = R.ReferenceJoinOperator(size, slide, offset)
+    side_stream = torch.cuda.Stream()
+    empty = torch.empty(0, dtype=torch.int64, device="cuda")
+    want = []
+    with W.GpuWindowJoinOperator(assigner(size, slide, offset), capacity_hint=16, max_batch=16) as op:
+        assert side_stream.cuda_stream != op.stream
+        for b in range(2):
+            for sd, (keys, ts, pay, batches) in enumerate(sides):
+                lo, hi, _ = batches[b]
+                cols = (keys[lo:hi], ts[lo:hi], pay[lo:hi])
+                ref.ingest(sd, *cols)
+                with torch.cuda.stream(side_stream):
+                    d = [torch.from_numpy(np.ascontiguousarray(c)).cuda(non_blocking=False) for c in cols]
+                    op.process_batch_device(sd, *d)
+                    del d
+                    op.process_batch_device(sd, empty, empty, empty)  # between this batch and the next
+            wm = min(sides[0][3][b][2], sides[1][3][b][2])
+            out = ref.advance_watermark(wm)
+            want.append(out)
+            assert op.advance_watermark(wm) == len(out[0])
+        want.append(ref.end_input())
+        assert op.end_input() == len(want[-1][0])
+        st = op.stats()
+        assert (st["live_left"], st["live_right"]) == (0, 0)
+        assert op.pending() == ref.pairs_fired and ref.pairs_fired > 20
+        R.check(op.drain(), [np.concatenate([w[c] for w in want]) for c in range(5)])
+    side_stream.synchronize()
+
+
 def test_operator_errors():
     with pytest.raises(N.GpuWinError) as e:
         W.GpuWindowJoinOperator(W.EventTimeSessionWindows.with_gap(5))
