@@ -7,11 +7,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <functional>
-#include <map>
 #include <memory>
-#include <set>
 #include <atomic>
 #include <chrono>
 #include <thread>
@@ -25,6 +22,7 @@
 #include <vector>
 #include <mutex>
 
+#include "gw_checkpoint.h"
 #include "gw_devmem.h"
 #include "gw_first.h"
 #include "gw_kernels.h"
@@ -71,19 +69,14 @@ struct HostProf {
     }
 };
 
-typedef __int128 i128;
-
-i128 floor_div(i128 a, i128 b) {  // b > 0
-    i128 q = a / b;
-    if ((a % b) != 0 && a < 0) --q;
-    return q;
-}
+using ckpt::i128;
+using ckpt::floor_div;
+using ckpt::fits64;
 i128 floor_mod(i128 a, i128 b) { return a - floor_div(a, b) * b; }
 int64_t gcd64(int64_t a, int64_t b) {
     while (b) { int64_t t = a % b; a = b; b = t; }
     return a;
 }
-bool fits64(i128 v) { return v >= (i128)INT64_MIN && v <= (i128)INT64_MAX; }
 
 // Both forms of the division by d: 64-bit dividends, and (gw_common.h make_udiv32) dividends
 // known to be below 2^32.
@@ -1687,19 +1680,8 @@ struct gw_handle {
         return GW_OK;
     }
     // Host copy of the map, sorted by key, for key groups at snapshot time.
-    struct KhmHost {
-        std::vector<std::pair<int64_t, int32_t>> kv;
-        bool has_min = false;
-        int32_t min_hash = 0;
-        bool on() const { return has_min || !kv.empty(); }
-        int32_t hash(int64_t key) const {
-            if (key == kEmptyKey) return has_min ? min_hash : java_long_hash(key);
-            auto it = std::lower_bound(kv.begin(), kv.end(), std::make_pair(key, INT32_MIN));
-            return it != kv.end() && it->first == key ? it->second : java_long_hash(key);
-        }
-    };
-    int khm_host(KhmHost& out) {
-        out = KhmHost{};
+    int khm_host(ckpt::KeyHashes& out) {
+        out = ckpt::KeyHashes{};
         if (!khm_used) return GW_OK;
         std::vector<int64_t> k((size_t)khm.cap + 1);
         std::vector<int32_t> h((size_t)khm.cap + 1);
@@ -1741,36 +1723,19 @@ struct gw_handle {
 
     // A restored blob's (key, hash) pairs, checked on the host before anything changes: one
     // hash per key within the blob and the same hash as the map already holds for that key.
-    int khm_check_host(const std::vector<int64_t>& keys, const std::vector<int32_t>& hashes) {
-        if (keys.empty()) return GW_OK;
-        std::vector<std::pair<int64_t, int32_t>> kv(keys.size());
-        for (size_t i = 0; i < keys.size(); ++i) kv[i] = {keys[i], hashes[i]};
-        std::sort(kv.begin(), kv.end());
-        for (size_t i = 1; i < kv.size(); ++i)
-            if (kv[i].first == kv[i - 1].first && kv[i].second != kv[i - 1].second)
-                return fail(GW_E_INVALID, "snapshot: a key with two different key hashes");
-        if (!khm_used) return GW_OK;
-        KhmHost kh;
-        int rc = khm_host(kh);
+    int khm_check_host(const ckpt::HashPairs& hp) {
+        snap::Err e = hp.check();
+        if (e) return fail(e);
+        if (hp.keys.empty() || !khm_used) return GW_OK;
+        ckpt::KeyHashes kh;
+        const int rc = khm_host(kh);
         if (rc) return rc;
-        for (const auto& e : kv) {
-            bool known = false;
-            int32_t h0 = 0;
-            if (e.first == kEmptyKey) {
-                known = kh.has_min;
-                h0 = kh.min_hash;
-            } else {
-                auto it = std::lower_bound(kh.kv.begin(), kh.kv.end(), std::make_pair(e.first, INT32_MIN));
-                if (it != kh.kv.end() && it->first == e.first) { known = true; h0 = it->second; }
-            }
-            if (known && h0 != e.second) return fail(GW_E_INVALID, "snapshot: a key with two different key hashes");
-        }
-        return GW_OK;
+        return (e = hp.check(kh)) ? fail(e) : GW_OK;
     }
 
     // ---------------------------------------------------------------- snapshot
-    // The blob format, its bounds-checked readers and its writer: gw_snapshot.h (gw::snap).
-    // Here: what needs the handle -- device collection, accumulators, key hashes, the overlay.
+    // The blob format: gw_snapshot.h (gw::snap); what a blob's entries mean: gw_checkpoint.h
+    // (gw::ckpt).  Here: the exact device state, its copy to host vectors, the overlay.
 
     // -------------------------------------------- restored window state (the overlay)
     // A heap-layout blob holds the reference's state per (key, window) and its timers.
@@ -1779,11 +1744,8 @@ struct gw_handle {
     // into the window's row together with the panes of the records that arrive after the
     // restore.  The watermark restarts at Long.MIN_VALUE as in the reference
     // (InternalTimerServiceImpl.java:72): nothing has fired, nothing is late.
-    struct OvEntry {
-        int64_t key, k, a0, a1;
-        uint32_t flags;
-    };
-    std::vector<OvEntry> ov_pending;  // restored, not yet on the device
+    static_assert(ckpt::kTimer == kOvTimer, "a restored window's timer flag");
+    std::vector<ckpt::WindowEntry> ov_pending;  // restored, not yet on the device
     DevBuf<int64_t> d_ov;             // key | k | a0 | a1, ov_n each
     DevBuf<uint32_t> d_ov_flags;
     DevBuf<int32_t> d_ov_head;        // [tv.cap + 1]
@@ -1822,9 +1784,7 @@ struct gw_handle {
     int ov_finalize() {
         if (ov_pending.empty()) return GW_OK;
         auto& v = ov_pending;
-        std::sort(v.begin(), v.end(), [](const OvEntry& x, const OvEntry& y) {
-            return x.key != y.key ? x.key < y.key : x.k < y.k;
-        });
+        std::sort(v.begin(), v.end(), ckpt::by_key_k);
         size_t w = 0;  // one entry per (key, window): merge repeats (the same key group twice)
         for (size_t i = 0; i < v.size(); ++i) {
             if (w && v[w - 1].key == v[i].key && v[w - 1].k == v[i].k) {
@@ -1877,85 +1837,42 @@ struct gw_handle {
         if (ov_n && clean_k_at(w) > ov_max_k && fired_k > ov_max_k) ov_free();
     }
 
-    // Accumulator <-> cell words (the serializer's value, gw_common.h cells).
-    void acc_to_be(std::vector<uint8_t>& o, int64_t a0, int64_t a1) const {
-        switch (cfg.agg) {
-        case GW_SUM_I32: snap::put32(o, (int32_t)(uint32_t)(uint64_t)a0); break;
-        case GW_MIN_F64: case GW_MAX_F64: snap::put64(o, f64_from_order_key(a0)); break;
-        case GW_AVG_I64: case GW_AVG_F64: snap::put64(o, a0); snap::put64(o, a1); break;
-        default: snap::put64(o, a0); break;
-        }
-    }
-    void acc_from_be(const uint8_t* p, int64_t& a0, int64_t& a1) const {
-        a1 = 0;
-        switch (cfg.agg) {
-        case GW_SUM_I32: a0 = (int64_t)snap::get32(p); break;
-        case GW_MIN_F64: case GW_MAX_F64: a0 = f64_order_key(snap::get64(p)); break;
-        case GW_AVG_I64: case GW_AVG_F64: a0 = snap::get64(p); a1 = snap::get64(p + 8); break;
-        default: a0 = snap::get64(p); break;
-        }
-    }
-    i128 win_start(i128 k) const { return (i128)cfg.offset + k * (i128)slide(); }
-
     int fail(const snap::Err& e) { return fail(e.code, "%s", e.reason); }
-    // The header of this handle's blobs.
-    snap::Header blob_header(uint32_t version, int32_t kg_lo, int32_t kg_hi, bool hashed) const {
-        snap::Header hd{};
-        hd.version = version;
-        hd.agg = cfg.agg; hd.assigner = cfg.assigner;
-        hd.size = cfg.size; hd.slide = cfg.slide; hd.offset = cfg.offset; hd.gap = cfg.gap;
-        hd.flags = hashed ? snap::kKeyHashes : 0;
-        hd.max_parallelism = cfg.max_parallelism; hd.kg_lo = kg_lo; hd.kg_hi = kg_hi;
-        return hd;
+    ckpt::Spec spec() const {  // what this handle's blobs depend on, in Spec's order
+        return {cfg.agg, cfg.assigner, cfg.trigger, cfg.max_parallelism, cfg.size, slide(), cfg.slide, cfg.offset, cfg.gap,
+                cfg.allowed_lateness, n, m, sess ? session_entry_words(sess) : 0};
     }
     int finish_blob(snap::Writer& w, const snap::Header& hd, void* buf, int64_t cap, int64_t* len) {
-        if (w.finish(hd, buf, cap, len)) return fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)*len);
-        return GW_OK;
+        return w.finish(hd, buf, cap, len) ? fail(GW_E_OUTPUT_FULL, "snapshot needs %lld bytes", (long long)*len) : GW_OK;
     }
-    // A window-layout state entry.
-    void put_state(std::vector<uint8_t>& st, int64_t s0, int64_t e0, int64_t key, const KhmHost& kh, int64_t a0,
-                   int64_t a1) const {
-        snap::put64(st, s0); snap::put64(st, e0); snap::put64(st, key);
-        if (kh.on()) snap::put32(st, kh.hash(key));
-        acc_to_be(st, a0, a1);
+    // The header and payload of a blob of this handle's kind; fresh: only before processing starts.
+    int open_blob(const ckpt::Spec& sp, const void* buf, int64_t len, bool fresh, snap::Header& hd, snap::Cursor& c) {
+        snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
+        if (e) return fail(e);
+        if (!sp.matches(hd)) return fail(GW_E_INVALID, "%s", ckpt::kOtherOperator);
+        if (fresh && (stats.events_in != 0 || wm != INT64_MIN))
+            return fail(GW_E_STATE, "restore after processing started (initializeState runs before the first record)");
+        return (e = snap::payload(buf, len, hd, c)) ? fail(e) : GW_OK;
     }
-    // A window's trigger timer (while it has not fired) and, under allowed lateness, its
-    // cleanup timer (registerCleanupTimer :631-643; with lateness 0 the two coincide).
-    void put_window_timers(std::vector<uint8_t>& tm, int32_t& ntm, bool trigger, int64_t key, int64_t s0, int64_t e0) const {
-        const i128 mx = (i128)e0 - 1, ct = mx + (i128)cfg.allowed_lateness;
-        if (trigger) {
-            snap::put_timer(tm, (int64_t)mx, key, s0, e0);
-            ntm++;
-        }
-        if (cfg.allowed_lateness > 0 && ct < (i128)INT64_MAX) {
-            snap::put_timer(tm, (int64_t)ct, key, s0, e0);
-            ntm++;
-        }
-    }
-
-    // Heap-layout snapshot (version 4) of the tumbling / sliding window state: per key group,
-    // the reference's "window-contents" entries (window, key, accumulator) -- every (key,
-    // window) whose panes hold data, folded, plus the restored windows -- the (empty)
-    // merging window set, and the event-time timers (CopyOnWriteStateMapSnapshot.writeState
-    // :127-149, TimerSerializer.serialize :147-152, InternalTimerServiceImpl :350-360):
-    //   state:   windows not fired yet; under allowed lateness with EventTimeTrigger also the
-    //            fired windows that are not cleaned yet (WindowOperator.cleanupTime :670-677);
-    //   timers:  maxTimestamp for the windows not fired yet (EventTimeTrigger.onElement),
-    //            maxTimestamp + lateness for every window with state when lateness > 0
-    //            (registerCleanupTimer :631-643; with lateness 0 the two coincide).
-    int snapshot_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
-        int rc;
+    int check_kg_range(int32_t kg_lo, int32_t kg_hi) {
         if (kg_lo < 0 || kg_hi < kg_lo || kg_hi >= cfg.max_parallelism)
             return fail(GW_E_INVALID, "key-group range [%d, %d] outside [0, %d)", kg_lo, kg_hi, cfg.max_parallelism);
+        return GW_OK;
+    }
+
+    // The tumbling / sliding window state (ckpt::encode_windows): the pane cells and parked
+    // entries of the exact device state, and the restored windows still holding state.
+    int snapshot_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
+        int rc;
+        if ((rc = check_kg_range(kg_lo, kg_hi))) return rc;
         if ((rc = ov_finalize())) return rc;
         if ((rc = ensure_fresh())) return rc;
         if ((rc = flush_buffer())) return rc;  // prepareSnapshotPreBarrier: buffered records first
         if (rf_bound && (rc = process_refire())) return rc;  // late records of fired windows
         if ((rc = refresh())) return rc;
-        KhmHost kh;  // keys fed with a key_hash: their key group comes from that hash
+        ckpt::KeyHashes kh;  // keys fed with a key_hash: their key group comes from that hash
         if ((rc = khm_host(kh))) return rc;
         const bool hashed = kh.on();
-        auto kg_of = [&](int64_t key) { return key_group_for_hash(kh.hash(key), cfg.max_parallelism); };
         // (key, pane, a0, a1, kg) of every non-null pane cell and parked entry in range
         const int64_t n_def = (int64_t)h_st->n_deferred;
         const int64_t bound = ((int64_t)h_st->used_slots + 1) * popcount(occ) + n_def;
@@ -1972,7 +1889,7 @@ struct gw_handle {
             a.d_key = def[cur][0]; a.d_pane = def[cur][1]; a.d_a0 = def[cur][2]; a.d_a1 = def[cur][3];
             a.n_def = n_def;
             a.max_p = cfg.max_parallelism;
-            a.kg_lo = hashed ? 0 : kg_lo;  // hashed keys: every entry, key groups on the host
+            a.kg_lo = hashed ? 0 : kg_lo;  // hashed keys: every entry, key groups on the host (encode_windows)
             a.kg_hi = hashed ? cfg.max_parallelism - 1 : kg_hi;
             a.o_key = d; a.o_pane = d + bound; a.o_a0 = d + 2 * bound; a.o_a1 = d + 3 * bound;
             a.o_kg = (int32_t*)(d + 4 * bound);
@@ -1991,481 +1908,82 @@ struct gw_handle {
                 if (n && e == hipSuccess) e = hipMemcpy(kgs.data(), a.o_kg, n * 4, hipMemcpyDeviceToHost);
             }
             if (e != hipSuccess) return fail(GW_E_DEVICE, "snapshot: %s", hipGetErrorString(e));
-            if (hashed) {  // key groups from the keys' own hashes, then the range filter
-                size_t w = 0;
-                for (size_t i = 0; i < kgs.size(); ++i) {
-                    const int32_t g = kg_of(col[0][i]);
-                    if (g < kg_lo || g > kg_hi) continue;
-                    for (int c = 0; c < 4; ++c) col[c][w] = col[c][i];
-                    kgs[w++] = g;
-                }
-                kgs.resize(w);
-                for (int c = 0; c < 4; ++c) col[c].resize(w);
-            }
         }
         // the restored windows still holding state
-        std::vector<OvEntry> ov;
+        std::vector<ckpt::WindowEntry> ov;
         if (ov_n) {
             std::vector<int64_t> oc((size_t)ov_n * 4);
             std::vector<uint32_t> of((size_t)ov_n);
             HIPCHECK(hipMemcpy(oc.data(), d_ov, (size_t)ov_n * 32, hipMemcpyDeviceToHost));
             HIPCHECK(hipMemcpy(of.data(), d_ov_flags, (size_t)ov_n * 4, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < ov_n; ++i) {
-                if (of[i] & kOvDead) continue;
-                const int32_t kg = kg_of(oc[i]);
-                if (kg < kg_lo || kg > kg_hi) continue;
-                ov.push_back(OvEntry{oc[i], oc[ov_n + i], oc[2 * ov_n + i], oc[3 * ov_n + i], of[i]});
-            }
+            for (int64_t i = 0; i < ov_n; ++i)
+                if (!(of[i] & kOvDead)) ov.push_back({oc[i], oc[ov_n + i], oc[2 * ov_n + i], oc[3 * ov_n + i], of[i]});
         }
         const bool lat = cfg.allowed_lateness > 0;
         const bool purging = cfg.trigger == GW_PURGING_EVENT_TIME_TRIGGER;
         const i128 state_lo = (lat && !purging) ? std::min(clean_k_at(wm), fired_k) : fired_k;
-        // entries of one key group: panes sorted by (key, pane), overlay by (key, k)
-        const int nk = kg_hi - kg_lo + 1;
-        std::vector<std::vector<int64_t>> by_kg(nk);  // indices into col
-        for (size_t i = 0; i < kgs.size(); ++i) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
-        std::vector<std::vector<OvEntry>> ov_kg(nk);
-        for (auto& e : ov) ov_kg[kg_of(e.key) - kg_lo].push_back(e);
         snap::Writer w;
-        const int64_t id0 = identity0(cfg.agg);
-        for (int g = 0; g < nk; ++g) {
-            w.begin_group();
-            auto& ix = by_kg[g];
-            std::sort(ix.begin(), ix.end(), [&](int64_t x, int64_t y) {
-                return col[0][x] != col[0][y] ? col[0][x] < col[0][y] : col[1][x] < col[1][y];
-            });
-            auto& oe = ov_kg[g];
-            std::sort(oe.begin(), oe.end(), [](const OvEntry& x, const OvEntry& y) {
-                return x.key != y.key ? x.key < y.key : x.k < y.k;
-            });
-            std::vector<uint8_t> st, tm;
-            int32_t nst = 0, ntm = 0;
-            size_t a = 0, b = 0;
-            while (a < ix.size() || b < oe.size()) {
-                // next key
-                int64_t key;
-                if (a < ix.size() && (b >= oe.size() || col[0][ix[a]] <= oe[b].key)) key = col[0][ix[a]];
-                else key = oe[b].key;
-                std::vector<std::pair<int64_t, std::pair<int64_t, int64_t>>> panes;  // pane -> cell
-                for (; a < ix.size() && col[0][ix[a]] == key; ++a) {
-                    const int64_t i = ix[a];
-                    if (!panes.empty() && panes.back().first == col[1][i]) {
-                        fold_cell(cfg.agg, panes.back().second.first, panes.back().second.second, col[2][i], col[3][i]);
-                    } else {
-                        panes.push_back({col[1][i], {col[2][i], col[3][i]}});
-                    }
-                }
-                std::vector<OvEntry> ok_;
-                for (; b < oe.size() && oe[b].key == key; ++b) ok_.push_back(oe[b]);
-                // the windows holding state: those covering a pane with data, and restored ones
-                std::vector<i128> ks;
-                for (auto& pp : panes) {
-                    const i128 p = pp.first;
-                    for (i128 k = floor_div(p - (i128)n, (i128)m) + 1; k <= floor_div(p, (i128)m); ++k) ks.push_back(k);
-                }
-                for (auto& e : ok_) ks.push_back(e.k);
-                std::sort(ks.begin(), ks.end());
-                ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
-                size_t q = 0;
-                for (i128 k : ks) {
-                    if (k < state_lo) continue;
-                    int64_t r0 = id0, r1 = 0;
-                    bool any = false;
-                    const i128 p0 = k * (i128)m, p1 = p0 + (i128)n;
-                    for (auto& pp : panes)
-                        if (pp.first >= p0 && pp.first < p1) {
-                            fold_cell(cfg.agg, r0, r1, pp.second.first, pp.second.second);
-                            any = true;
-                        }
-                    bool timer = any && k >= fired_k;
-                    while (q < ok_.size() && ok_[q].k < k) ++q;
-                    if (q < ok_.size() && ok_[q].k == k) {
-                        fold_cell(cfg.agg, r0, r1, ok_[q].a0, ok_[q].a1);
-                        any = true;
-                        if ((ok_[q].flags & kOvTimer) && k >= fired_k) timer = true;
-                    }
-                    if (!any) continue;
-                    const i128 s0 = win_start(k), e0 = s0 + (i128)size();
-                    if (!fits64(s0) || !fits64(e0)) return fail(GW_E_RANGE, "window bounds overflow int64");
-                    put_state(st, (int64_t)s0, (int64_t)e0, key, kh, r0, r1);
-                    nst++;
-                    put_window_timers(tm, ntm, timer, key, (int64_t)s0, (int64_t)e0);
-                }
-            }
-            w.section(nst, st);
-            w.section(0, {});  // merging window set: none for tumbling / sliding windows
-            w.section(ntm, tm);
-        }
-        snap::Header hd = blob_header(4, kg_lo, kg_hi, hashed);
-        hd.slide = slide();
-        return finish_blob(w, hd, buf, cap, len);
+        snap::Header hd;
+        const snap::Err e = ckpt::encode_windows(spec(), kh, kg_lo, kg_hi, col, kgs, ov, fired_k, state_lo, w, hd);
+        return e ? fail(e) : finish_blob(w, hd, buf, cap, len);
     }
 
     // Restore one heap-layout blob (any key-group range; several calls after rescaling).
-    // Only before the first record or watermark, as initializeState runs before processing.
-    // The blob is parsed and checked whole (windows, counts, key hashes against each other
-    // and against the keys the handle already knows) before anything changes, so a rejected
-    // blob leaves the handle as it was; `dry` stops there (composite handles check every
-    // class's part before restoring any).
+    // The blob is parsed and checked whole (windows, counts, key hashes against each other and
+    // against the keys the handle already knows) before anything changes, so a rejected blob leaves
+    // the handle as it was; `dry` stops there (composites check every class's part first).
     int restore_heap(const void* buf, int64_t len, bool dry = false) {
+        const ckpt::Spec sp = spec();
         snap::Header hd;
         snap::Cursor c;
-        snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
-        if (e) return fail(e);
-        if (hd.version != 4 || hd.agg != cfg.agg || hd.assigner != cfg.assigner || hd.size != cfg.size ||
-            hd.slide != slide() || hd.offset != cfg.offset || hd.max_parallelism != cfg.max_parallelism)
-            return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-        if (stats.events_in != 0 || wm != INT64_MIN)
-            return fail(GW_E_STATE, "restore after processing started (initializeState runs before the first record)");
-        if ((e = snap::payload(buf, len, hd, c))) return fail(e);
-        hd.flags &= snap::kKeyHashes;  // entries of this handle's width, whatever else the blob claims
-        const bool hashed = hd.flags != 0;
-        const int64_t acc_at = snap::state_acc_at(hd);
-        std::vector<OvEntry> pend;  // the blob's entries, appended to ov_pending once all is checked
-        std::vector<int64_t> hkeys;  // (key, hash) of a hashed blob's entries
-        std::vector<int32_t> hvals;
-        std::vector<const uint8_t*> timers;  // of the current key group
-        size_t base = 0;                     // its first entry in pend
-        auto by_key_k = [](const OvEntry& x, const OvEntry& y) { return x.key != y.key ? x.key < y.key : x.k < y.k; };
-        auto win_k = [&](int64_t s0) { return floor_div((i128)s0 - cfg.offset, (i128)slide()); };
-        e = snap::walk_windows(
-            hd, c,
-            [&](const uint8_t* p) {
-                const int64_t s0 = snap::state_start(p), e0 = snap::state_end(p), key = snap::state_key(p);
-                const i128 k = win_k(s0);
-                if (win_start(k) != (i128)s0 || (i128)s0 + size() != (i128)e0) {
-                    fail(GW_E_INVALID, "snapshot window [%lld, %lld) is not a window of this assigner", (long long)s0,
-                         (long long)e0);
-                    return snap::invalid(err.c_str());
-                }
-                OvEntry o{key, (int64_t)k, 0, 0, 0};
-                if (hashed) {
-                    hkeys.push_back(key);
-                    hvals.push_back(snap::state_hash(p));
-                }
-                acc_from_be(p + acc_at, o.a0, o.a1);
-                pend.push_back(o);
-                return snap::Err{};
-            },
-            snap::NoSets{"merging window set in a tumbling / sliding snapshot"},
-            [&](const uint8_t* t) { timers.push_back(t); },
-            [&] {
-                // an event-time timer at the window's maxTimestamp: the window has not fired
-                std::sort(pend.begin() + base, pend.end(), by_key_k);
-                for (const uint8_t* t : timers) {
-                    // a cleanup timer: implied by the state
-                    if (snap::timer_time(t) != (int64_t)((uint64_t)snap::timer_end(t) - 1)) continue;
-                    const OvEntry want{snap::timer_key(t), (int64_t)win_k(snap::timer_start(t)), 0, 0, 0};
-                    auto it = std::lower_bound(pend.begin() + base, pend.end(), want, by_key_k);
-                    if (it != pend.end() && it->key == want.key && it->k == want.k) it->flags |= kOvTimer;
-                }
-                timers.clear();
-                base = pend.size();
-            });
-        if (e) return fail(e);
-        int rc = khm_check_host(hkeys, hvals);
-        if (rc || dry) return rc;
+        int rc = open_blob(sp, buf, len, true, hd, c);
+        if (rc) return rc;
+        std::vector<ckpt::WindowEntry> pend;  // the blob's entries, appended to ov_pending once all is checked
+        ckpt::HashPairs hp;
+        std::string why;
+        const snap::Err e = ckpt::decode_windows(sp, hd, c, pend, hp, why);
+        if ((rc = e ? fail(e) : khm_check_host(hp)) || dry) return rc;
         ov_pending.insert(ov_pending.end(), pend.begin(), pend.end());
-        return khm_insert_host(hkeys, hvals);
+        return khm_insert_host(hp.keys, hp.hashes);
     }
 
-    // Session windows (blob version 4, the heap layout of snapshot_heap): per key group the
-    // "window-contents" entries of the in-flight sessions, the merging window sets and the
-    // event-time timers (snapshot_sessions_heap).  Count windows (version 3): per key, the
-    // element count and the ring of count-pane accumulators -- the CountTrigger count and
-    // the window contents the evicting operator keeps (EvictingWindowOperator.java:92-135).
-    uint32_t slot_blob_version() const { return cfg.assigner == GW_COUNT_SLIDING ? 3u : 4u; }
-
-    // The slot table's entries of [kg_lo, kg_hi] with their key groups (by the key's own hash
-    // when the keys came with one).
-    int collect_slots(int32_t kg_lo, int32_t kg_hi, KhmHost& kh, std::vector<int64_t>& ent, std::vector<int32_t>& kgs) {
+    // Session and count windows: the slot table's entries of [kg_lo, kg_hi] with their key
+    // groups (by the key's own hash when the keys came with one), then their encoder.
+    int snapshot_sessions(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
         int rc;
+        if ((rc = check_kg_range(kg_lo, kg_hi))) return rc;
         if ((rc = session_refresh(sess, err))) return fail(rc, "%s", err.c_str());
+        ckpt::KeyHashes kh;
         if ((rc = khm_host(kh))) return rc;
         std::function<int32_t(int64_t)> hash_of;
         if (kh.on()) hash_of = [&](int64_t k) { return kh.hash(k); };
+        std::vector<int64_t> ent;
+        std::vector<int32_t> kgs;
         if ((rc = session_collect(sess, kg_lo, kg_hi, ent, kgs, err, hash_of))) return fail(rc, "%s", err.c_str());
-        return GW_OK;
-    }
-
-    // A tumbling count window in the heap layout (blob version 4, snap::walk_count_windows):
-    // the contents are the current count pane (a tumbling count window is one pane).  A key
-    // whose element count is a multiple of size was just purged and holds no state.  The
-    // sliding form keeps the version-3 layout.
-    int snapshot_count_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
-        int rc;
-        KhmHost kh;
-        std::vector<int64_t> ent;
-        std::vector<int32_t> kgs;
-        if ((rc = collect_slots(kg_lo, kg_hi, kh, ent, kgs))) return rc;
-        const int64_t ew = session_entry_words(sess), W = tv.words;
-        const int64_t ring = (ew - 2) / W;
-        const int nk = kg_hi - kg_lo + 1;
-        std::vector<std::vector<int64_t>> by_kg(nk);
-        for (size_t i = 0; i < kgs.size(); ++i) {
-            const int64_t c = ent[ew * i + 1];
-            if (c % cfg.size != 0) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
-        }
+        const auto encode = is_session(cfg.assigner)             ? ckpt::encode_sessions
+                            : cfg.assigner == GW_COUNT_TUMBLING ? ckpt::encode_count
+                                                                : ckpt::encode_slots;
         snap::Writer w;
-        for (int g = 0; g < nk; ++g) {
-            w.begin_group();
-            auto& ix = by_kg[g];
-            std::sort(ix.begin(), ix.end(), [&](int64_t x, int64_t y) { return ent[ew * x] < ent[ew * y]; });
-            std::vector<uint8_t> st, cnt;
-            for (int64_t i : ix) {
-                const int64_t* e = &ent[ew * i];
-                const int64_t key = e[0], c = e[1];
-                const int64_t* cell = e + 2 + (((c - 1) / cfg.size) % ring) * W;  // the current count pane
-                for (std::vector<uint8_t>* v : {&st, &cnt}) {  // (GlobalWindow, key, [hash,] ...
-                    v->push_back(0);
-                    snap::put64(*v, key);
-                    if (kh.on()) snap::put32(*v, kh.hash(key));
-                }
-                acc_to_be(st, cell[0], W == 2 ? cell[1] : 0);
-                snap::put64(cnt, c % cfg.size);
-            }
-            w.section((int32_t)ix.size(), st);
-            w.section((int32_t)ix.size(), cnt);
-            w.section(0, {});  // no timers
-        }
-        return finish_blob(w, blob_header(4, kg_lo, kg_hi, kh.on()), buf, cap, len);
-    }
-    // ... and back into version-3 entries (key, element count = the trigger's count, the
-    // contents in count pane 0 of the ring, identities elsewhere)
-    int parse_count_heap(const snap::Header& hd, snap::Cursor c, std::vector<int64_t>& ent, std::vector<int64_t>& hkeys,
-                         std::vector<int32_t>& hvals) {
-        const int64_t at = snap::count_value_at(hd);
-        const bool hashed = snap::hash_bytes(hd) != 0;
-        const int64_t ew = session_entry_words(sess), W = tv.words;
-        snap::Entries st{};
-        const snap::Err e = snap::walk_count_windows(
-            hd, c, [&](snap::Entries contents) { st = contents; },
-            [&](snap::Entries counts) {
-                if (counts.n != st.n) return snap::invalid("count-window contents without their CountTrigger count");
-                for (int32_t i = 0; i < st.n; ++i) {
-                    const uint8_t* x = st[i];
-                    const uint8_t* q = counts[i];
-                    const int64_t key = snap::get64(x + snap::kCountKeyAt), cnt = snap::get64(q + at);
-                    if (x[0] != 0 || q[0] != 0 || snap::get64(q + snap::kCountKeyAt) != key || cnt <= 0 || cnt >= cfg.size)
-                        return snap::invalid("corrupt count-window snapshot entry");
-                    if (hashed) {
-                        hkeys.push_back(key);
-                        hvals.push_back(snap::get32(x + snap::kCountHashAt));
-                    }
-                    const size_t o = ent.size();
-                    ent.resize(o + (size_t)ew, 0);
-                    ent[o] = key;
-                    ent[o + 1] = cnt;
-                    // identities, then the contents in pane 0
-                    for (int64_t r = 2; r < ew; r += W) ent[o + r] = identity0(cfg.agg);
-                    int64_t a0, a1;
-                    acc_from_be(x + at, a0, a1);
-                    ent[o + 2] = a0;
-                    if (W == 2) ent[o + 3] = a1;
-                }
-                return snap::Err{};
-            });
-        return e ? fail(e) : GW_OK;
-    }
-
-    // Session windows in the heap backend's layout (snap::walk_windows).  The GPU keeps a
-    // session's state under the session itself, so its state window is the window; a fired
-    // session under PurgingTrigger holds no state (its contents were purged,
-    // WindowOperator.java:482-484) and has no entry.  Timers: the trigger's timer at
-    // maxTimestamp while the session has not fired (EventTimeTrigger.onElement / onMerge)
-    // and, under allowed lateness, its cleanup timer.
-    // Order: keys ascending, a key's sessions by start, its timers by (window, time).
-    int snapshot_sessions_heap(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
-        int rc;
-        KhmHost kh;
-        std::vector<int64_t> ent;  // (key, start, end, a0, a1, fired) per session
-        std::vector<int32_t> kgs;
-        if ((rc = collect_slots(kg_lo, kg_hi, kh, ent, kgs))) return rc;
-        const int nk = kg_hi - kg_lo + 1;
-        std::vector<std::vector<int64_t>> by_kg(nk);
-        for (size_t i = 0; i < kgs.size(); ++i) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
-        const bool purging = cfg.trigger == GW_PURGING_EVENT_TIME_TRIGGER;
-        snap::Writer w;
-        for (int g = 0; g < nk; ++g) {
-            w.begin_group();
-            auto& ix = by_kg[g];
-            std::sort(ix.begin(), ix.end(), [&](int64_t x, int64_t y) {
-                const int64_t* a = &ent[6 * x];
-                const int64_t* b = &ent[6 * y];
-                return a[0] != b[0] ? a[0] < b[0] : a[1] < b[1];
-            });
-            std::vector<uint8_t> st, ms, tm;
-            int32_t nst = 0, nms = 0, ntm = 0;
-            for (size_t a = 0; a < ix.size();) {
-                const int64_t key = ent[6 * ix[a]];
-                size_t b = a;
-                while (b < ix.size() && ent[6 * ix[b]] == key) ++b;
-                snap::put64(ms, key);
-                if (kh.on()) snap::put32(ms, kh.hash(key));
-                snap::put32(ms, (int32_t)(b - a));
-                nms++;
-                for (size_t q = a; q < b; ++q) {
-                    const int64_t* x = &ent[6 * ix[q]];
-                    const int64_t s0 = x[1], e0 = x[2];
-                    const bool fired = x[5] != 0;
-                    snap::put64(ms, s0); snap::put64(ms, e0); snap::put64(ms, s0); snap::put64(ms, e0);
-                    if (!(purging && fired)) {
-                        put_state(st, s0, e0, key, kh, x[3], x[4]);
-                        nst++;
-                    }
-                    put_window_timers(tm, ntm, !fired, key, s0, e0);
-                }
-                a = b;
-            }
-            w.section(nst, st);
-            w.section(nms, ms);
-            w.section(ntm, tm);
-        }
-        return finish_blob(w, blob_header(4, kg_lo, kg_hi, kh.on()), buf, cap, len);
-    }
-
-    // Reads a session blob of the heap layout back into (key, start, end, a0, a1, fired)
-    // sessions: each merging-window-set mapping (window -> state window) takes the state of
-    // its state window (any original window, as the reference's MergingWindowSet.addWindow
-    // keeps it, :188-201), or none; a session has fired when its trigger timer at
-    // maxTimestamp is gone.  A session without state that has not fired is a trigger outside
-    // EventTimeTrigger / PurgingTrigger (GW_E_UNSUPPORTED); state no mapping names, or
-    // overlapping sessions of one key, are a corrupt blob.
-    int parse_session_heap(const snap::Header& hd, snap::Cursor c, std::vector<int64_t>& out, std::vector<int64_t>& hkeys,
-                           std::vector<int32_t>& hvals) {
-        const bool hashed = snap::hash_bytes(hd) != 0;
-        const int64_t acc_at = snap::state_acc_at(hd);
-        const int64_t id0 = cfg.agg == GW_AVG_F64 ? INT64_MIN : identity0(cfg.agg);  // a purged session
-        typedef std::tuple<int64_t, int64_t, int64_t> KW;  // (key, start, end)
-        // of the current key group:
-        std::map<KW, std::pair<std::pair<int64_t, int64_t>, bool>> state;  // -> (acc, used)
-        std::vector<std::array<int64_t, 5>> ses;  // (key, start, end, state start, state end)
-        std::set<KW> armed;  // sessions whose trigger timer (at maxTimestamp) is still set
-        const snap::Err e = snap::walk_windows(
-            hd, c,
-            [&](const uint8_t* p) {
-                const int64_t key = snap::state_key(p);
-                int64_t a0, a1;
-                acc_from_be(p + acc_at, a0, a1);
-                if (hashed) { hkeys.push_back(key); hvals.push_back(snap::state_hash(p)); }
-                const KW kw{key, snap::state_start(p), snap::state_end(p)};
-                if (!state.emplace(kw, std::make_pair(std::make_pair(a0, a1), false)).second)
-                    return snap::invalid("two state entries of one (key, window) in a snapshot key group");
-                return snap::Err{};
-            },
-            [&](const uint8_t* head, int32_t n, const uint8_t* win) {
-                const int64_t key = snap::get64(head);
-                if (hashed) { hkeys.push_back(key); hvals.push_back(snap::get32(head + snap::kSetHashAt)); }
-                for (int32_t j = 0; j < n; ++j, win += snap::kSetWindowBytes)
-                    ses.push_back({key, snap::get64(win), snap::get64(win + 8), snap::get64(win + 16), snap::get64(win + 24)});
-            },
-            [&](const uint8_t* t) {
-                const int64_t e0 = snap::timer_end(t);
-                if (snap::timer_time(t) == (int64_t)((uint64_t)e0 - 1))
-                    armed.insert(KW{snap::timer_key(t), snap::timer_start(t), e0});
-            },
-            [&] {
-                std::sort(ses.begin(), ses.end());
-                for (size_t i = 0; i < ses.size(); ++i) {
-                    const auto& x = ses[i];
-                    if (x[2] <= x[1]) return snap::invalid("empty session window in a snapshot");
-                    if (i && ses[i - 1][0] == x[0] && ses[i - 1][2] >= x[1])  // TimeWindow.intersects is inclusive
-                        return snap::invalid("overlapping sessions of one key in a snapshot");
-                    const bool fired = armed.count(KW{x[0], x[1], x[2]}) == 0;
-                    auto it = state.find(KW{x[0], x[3], x[4]});
-                    int64_t a0 = id0, a1 = 0;
-                    if (it != state.end()) {
-                        if (it->second.second) return snap::invalid("two sessions share one state window");
-                        it->second.second = true;
-                        a0 = it->second.first.first;
-                        a1 = it->second.first.second;
-                    } else if (!fired) {
-                        return snap::Err{GW_E_UNSUPPORTED, "a session without state whose timer has not fired "
-                                                           "(a trigger other than EventTimeTrigger / PurgingTrigger)"};
-                    }
-                    out.insert(out.end(), {x[0], x[1], x[2], a0, a1, (int64_t)fired});
-                }
-                for (auto& kv : state)
-                    if (!kv.second.second) return snap::invalid("a state entry outside every merging window set");
-                state.clear();
-                ses.clear();
-                armed.clear();
-                return snap::Err{};
-            });
-        return e ? fail(e) : GW_OK;
-    }
-
-    int snapshot_sessions(int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
-        int rc;
-        if (kg_lo < 0 || kg_hi < kg_lo || kg_hi >= cfg.max_parallelism)
-            return fail(GW_E_INVALID, "key-group range [%d, %d] outside [0, %d)", kg_lo, kg_hi, cfg.max_parallelism);
-        if (is_session(cfg.assigner)) return snapshot_sessions_heap(kg_lo, kg_hi, buf, cap, len);
-        if (cfg.assigner == GW_COUNT_TUMBLING) return snapshot_count_heap(kg_lo, kg_hi, buf, cap, len);
-        KhmHost kh;
-        std::vector<int64_t> ent;
-        std::vector<int32_t> kgs;
-        if ((rc = collect_slots(kg_lo, kg_hi, kh, ent, kgs))) return rc;
-        // fixed entries in key-group order, collection order within a key group; with key
-        // hashes each entry gets the key's hash as one more word
-        const int64_t ew = session_entry_words(sess);
-        const int nk = kg_hi - kg_lo + 1;
-        std::vector<std::vector<int64_t>> by_kg(nk);
-        for (size_t i = 0; i < kgs.size(); ++i) by_kg[kgs[i] - kg_lo].push_back((int64_t)i);
-        snap::Writer w;
-        for (int g = 0; g < nk; ++g) {
-            w.begin_group();
-            for (int64_t i : by_kg[g]) {
-                w.bytes((const uint8_t*)&ent[ew * i], ew * 8);
-                if (kh.on()) {
-                    const int64_t hw = (int64_t)kh.hash(ent[ew * i]);
-                    w.bytes((const uint8_t*)&hw, 8);
-                }
-            }
-        }
-        snap::Header hd = blob_header(slot_blob_version(), kg_lo, kg_hi, kh.on());
-        hd.offset = 0;
-        hd.reserved = (int32_t)(ew + (kh.on() ? 1 : 0));
+        const snap::Header hd = encode(spec(), kh, kg_lo, kg_hi, ent, kgs, w);
         return finish_blob(w, hd, buf, cap, len);
     }
 
     int restore_sessions(const void* buf, int64_t len, bool dry = false) {
+        const ckpt::Spec sp = spec();
         snap::Header hd;
         snap::Cursor c;
-        snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
-        if (e) return fail(e);
-        const int64_t ew0 = session_entry_words(sess), ew = ew0 + snap::hash_bytes(hd) / 4;  // fixed entries: words
-        bool same = hd.version == slot_blob_version() && hd.agg == cfg.agg && hd.assigner == cfg.assigner &&
-                    hd.max_parallelism == cfg.max_parallelism;
-        if (is_session(cfg.assigner)) same = same && hd.gap == cfg.gap && !(hd.flags & ~snap::kKeyHashes);
-        else if (cfg.assigner == GW_COUNT_TUMBLING) same = same && hd.size == cfg.size && !(hd.flags & ~snap::kKeyHashes);
-        else same = same && hd.gap == cfg.gap && hd.size == cfg.size && hd.slide == cfg.slide && hd.reserved == (int32_t)ew;
-        if (!same) return fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-        if ((e = snap::payload(buf, len, hd, c))) return fail(e);
-        std::vector<int64_t> ent, hkeys;
-        std::vector<int32_t> hvals;
-        int rc = GW_OK;
-        if (is_session(cfg.assigner)) {
-            rc = parse_session_heap(hd, c, ent, hkeys, hvals);
-        } else if (cfg.assigner == GW_COUNT_TUMBLING) {
-            rc = parse_count_heap(hd, c, ent, hkeys, hvals);
-        } else {
-            ent.resize((size_t)(hd.entries * ew0));
-            for (int64_t i = 0; i < hd.entries; ++i) {  // aligned copy without the hash words
-                const uint8_t* x = c.take(ew * 8);
-                memcpy(&ent[i * ew0], x, (size_t)ew0 * 8);
-                if (ew > ew0) {
-                    int64_t hw;
-                    memcpy(&hw, x + ew0 * 8, 8);
-                    hkeys.push_back(ent[i * ew0]);
-                    hvals.push_back((int32_t)hw);
-                }
-            }
-        }
-        if (rc == GW_OK) rc = khm_check_host(hkeys, hvals);  // before the table changes
-        if (rc || dry) return rc;
-        rc = session_restore(sess, ent.data(), (int64_t)ent.size() / ew0, err);
+        int rc = open_blob(sp, buf, len, false, hd, c);
+        if (rc) return rc;
+        std::vector<int64_t> ent;
+        ckpt::HashPairs hp;
+        const auto decode = is_session(cfg.assigner)             ? ckpt::decode_sessions
+                            : cfg.assigner == GW_COUNT_TUMBLING ? ckpt::decode_count
+                                                                : ckpt::decode_slots;
+        const snap::Err e = decode(sp, hd, c, ent, hp);
+        if ((rc = e ? fail(e) : khm_check_host(hp)) || dry) return rc;  // before the table changes
+        rc = session_restore(sess, ent.data(), (int64_t)ent.size() / sp.ew, err);
         if (rc) return fail(rc, "%s", err.c_str());
-        return khm_insert_host(hkeys, hvals);
+        return khm_insert_host(hp.keys, hp.hashes);
     }
 
 #ifndef GW_FAST_FIRE
@@ -4246,11 +3764,8 @@ int gw_flush(gw_handle* h) {
     return rc ? rc : h->flush_buffer();
 }
 
-// Window-class composite snapshots: the children's heap-layout blobs merged per key group
-// (their (window, key, state) entries and timers are disjoint by window), under the
-// composite's own assigner header; restore splits each key group's entries and timers by
-// the class of their window.  The layout: snap::walk_windows, without merging window sets.
-static int64_t comp_slide(const gw_handle* h) { return h->cfg.assigner == GW_TUMBLING ? h->cfg.size : h->cfg.slide; }
+// Window-class composites: the children's blobs merged per key group under the composite's own
+// header (ckpt::merge_classes); restore cuts the blob into one part per class (ckpt::cut_classes).
 static int kid_snapshot(gw_handle* h, gw_handle* kid, int32_t kg_lo, int32_t kg_hi, std::vector<uint8_t>& blob) {
     int64_t l = 0;
     int rc = gw_snapshot(kid, kg_lo, kg_hi, nullptr, 0, &l);
@@ -4264,44 +3779,14 @@ static int comp_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, 
     const int64_t nk = (int64_t)kg_hi - kg_lo + 1;
     if (kg_lo < 0 || nk <= 0) return h->fail(GW_E_INVALID, "bad key-group range");
     std::vector<std::vector<uint8_t>> blobs(h->kids.size());
-    // per key group, the classes' entries by (key, window) and timers by (key, window, time bytes)
-    std::vector<std::vector<std::pair<std::pair<int64_t, int64_t>, const uint8_t*>>> st(nk);
-    std::vector<std::vector<std::pair<std::tuple<int64_t, int64_t, uint64_t>, const uint8_t*>>> tm(nk);
-    snap::Header hd{};  // kids[0]'s: every class sees every batch, so all or none carry key hashes
     for (size_t j = 0; j < h->kids.size(); ++j) {
-        int rc = kid_snapshot(h, h->kids[j], kg_lo, kg_hi, blobs[j]);
+        const int rc = kid_snapshot(h, h->kids[j], kg_lo, kg_hi, blobs[j]);
         if (rc) return rc;
-        snap::Header kh;
-        snap::Cursor c;
-        snap::Err e = snap::open(blobs[j].data(), (int64_t)blobs[j].size(), 4, 4, kh, c);
-        if (e) return h->fail(e);
-        if (j && kh.flags != hd.flags) return h->fail(GW_E_STATE, "window classes disagree on key hashes");
-        if (!j) hd = kh;
-        int64_t g = 0;
-        e = snap::walk_windows(
-            kh, c, [&](const uint8_t* p) { st[g].push_back({{snap::state_key(p), snap::state_start(p)}, p}); }, snap::NoSets{},
-            [&](const uint8_t* t) {
-                tm[g].push_back({{snap::timer_key(t), snap::timer_start(t), (uint64_t)snap::get64(t)}, t});
-            },
-            [&] { ++g; });
-        if (e) return h->fail(e);
     }
-    const int64_t eb = snap::state_entry_bytes(hd);
     snap::Writer w;
-    for (int64_t g = 0; g < nk; ++g) {  // snapshot_heap's order
-        std::sort(st[g].begin(), st[g].end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        std::sort(tm[g].begin(), tm[g].end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        w.begin_group();
-        w.count((int32_t)st[g].size());
-        for (auto& e : st[g]) w.bytes(e.second, eb);
-        w.count(0);
-        w.count((int32_t)tm[g].size());
-        for (auto& e : tm[g]) w.bytes(e.second, snap::kTimerBytes);
-    }
-    hd.assigner = h->cfg.assigner;
-    hd.slide = comp_slide(h);
-    hd.offset = h->cfg.offset;
-    return h->finish_blob(w, hd, buf, cap, len);
+    snap::Header hd;
+    const snap::Err e = ckpt::merge_classes(h->spec(), blobs, kg_lo, kg_hi, w, hd);
+    return e ? h->fail(e) : h->finish_blob(w, hd, buf, cap, len);
 }
 
 static int restore_any(gw_handle* h, const void* buf, int64_t len, bool dry);
@@ -4320,55 +3805,17 @@ static int restore_parts(gw_handle* h, const std::vector<gw_handle*>& kids, cons
 
 // Window classes: the blob is cut into one part per class.
 static int comp_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
+    const ckpt::Spec sp = h->spec();
     snap::Header hd;
     snap::Cursor c;
-    snap::Err e = snap::header(buf, len, 1, snap::kMaxVersion, hd);
+    int rc = h->open_blob(sp, buf, len, false, hd, c);
+    if (rc) return rc;
+    std::vector<ckpt::Spec> classes;
+    for (gw_handle* kid : h->kids) classes.push_back(kid->spec());
+    std::vector<std::vector<uint8_t>> blobs;
+    const snap::Err e = ckpt::cut_classes(sp, classes, hd, c, blobs);
     if (e) return h->fail(e);
-    if (hd.version != 4 || hd.agg != h->cfg.agg || hd.assigner != h->cfg.assigner || hd.size != h->cfg.size ||
-        hd.slide != comp_slide(h) || hd.offset != h->cfg.offset || hd.max_parallelism != h->cfg.max_parallelism)
-        return h->fail(GW_E_INVALID, "snapshot of a different window / aggregate / max parallelism");
-    if ((e = snap::payload(buf, len, hd, c))) return h->fail(e);
-    const int64_t J = (int64_t)h->kids.size();
-    snap::Header lay = hd;  // entries of the classes' width (restore_heap)
-    lay.flags &= snap::kKeyHashes;
-    const int64_t eb = snap::state_entry_bytes(lay);
-    auto cls = [&](int64_t s0) {  // window class of a window start
-        const int64_t k = (int64_t)floor_div((i128)s0 - h->cfg.offset, (i128)comp_slide(h));
-        return (size_t)(((k % J) + J) % J);
-    };
-    std::vector<snap::Writer> w(J);
-    std::vector<std::vector<uint8_t>> st(J), tm(J);  // of the current key group
-    e = snap::walk_windows(
-        lay, c,
-        [&](const uint8_t* p) {
-            const size_t j = cls(snap::state_start(p));
-            st[j].insert(st[j].end(), p, p + eb);
-        },
-        snap::NoSets{"merging window set in a sliding snapshot"},
-        [&](const uint8_t* t) {
-            const size_t j = cls(snap::timer_start(t));
-            tm[j].insert(tm[j].end(), t, t + snap::kTimerBytes);
-        },
-        [&] {
-            for (int64_t j = 0; j < J; ++j) {
-                w[j].begin_group();
-                w[j].section((int32_t)(st[j].size() / eb), st[j]);
-                w[j].section(0, {});
-                w[j].section((int32_t)(tm[j].size() / snap::kTimerBytes), tm[j]);
-                st[j].clear();
-                tm[j].clear();
-            }
-        });
-    if (e) return h->fail(e);
-    std::vector<std::vector<uint8_t>> blobs(J);
-    for (int64_t j = 0; j < J; ++j) {
-        snap::Header kh = hd;
-        kh.assigner = h->kids[j]->cfg.assigner;
-        kh.slide = h->kids[j]->cfg.slide;
-        kh.offset = h->kids[j]->cfg.offset;
-        blobs[j] = w[j].finish(kh);
-    }
-    const int rc = restore_parts(h, h->kids, blobs, true);
+    rc = restore_parts(h, h->kids, blobs, true);
     return rc || dry ? rc : restore_parts(h, h->kids, blobs, false);
 }
 
@@ -4378,95 +3825,49 @@ static int comp_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
         if (e_ != hipSuccess) return (h)->fail(GW_E_DEVICE, "%s failed: %s", #x, hipGetErrorString(e_)); \
     } while (0)
 
-// ---- first-element handles: one heap-layout blob for both operators -------------------
-// The reference keeps one reduced Tuple per (key, window): the window's first element with
-// the aggregated field replaced (HeapReducingState.java:90-97, SumAggregator /
-// ComparableAggregator).  The blob holds exactly that per entry: (window, key, [hash],
-// aggregate, payload of the first element) with flags |= snap::kFirstElement, and kids[0]'s
-// timers.  A restore gives the restored first elements new arrival sequences: their payloads
-// go to the log, kids[1] gets (window, key, new sequence) entries.
-// minBy / maxBy handles hold the same entries: the element's payload comes from the log
-// (fe_by_select over the entries' (key, window, MIN / MAX)) instead of kids[1]'s sequence.
+// ---- first-element handles: one heap-layout blob for both operators (ckpt::FirstElementJoin,
+// FirstElementSplit).  A restore gives the restored first elements new arrival sequences: their
+// payloads go to the log, kids[1] gets (window, key, new sequence) entries.  minBy / maxBy: the
+// element's payload comes from the log (fe_by_select over the entries' (key, window, MIN / MAX)).
 static int fe_snapshot(gw_handle* h, int32_t kg_lo, int32_t kg_hi, void* buf, int64_t cap, int64_t* len) {
     gw_handle* A = h->kids[0];
     std::vector<uint8_t> ba, bb;  // the operators' blobs (minBy / maxBy: one operator)
     int rc = kid_snapshot(h, A, kg_lo, kg_hi, ba);
     if (rc == GW_OK && !h->fe_by) rc = kid_snapshot(h, h->kids[1], kg_lo, kg_hi, bb);
     if (rc) return rc;
-    snap::Header ha, hb;
-    snap::Cursor ca, cb;
-    if (snap::open(ba.data(), (int64_t)ba.size(), 4, 4, ha, ca) ||
-        (!h->fe_by && (snap::open(bb.data(), (int64_t)bb.size(), 4, 4, hb, cb) || ha.flags != hb.flags)))
-        return h->fail(GW_E_STATE, "first-element snapshot: the operators' blobs differ");
-    // pass 1: kids[0]'s entries and timers (with their counts at each key group's end), and
-    // the sequences of every entry's first element, in entry order
-    std::vector<const uint8_t*> sa, ta, sb;
-    std::vector<std::pair<size_t, size_t>> ends;
-    std::vector<size_t> ends_b;
-    snap::Err bad = snap::walk_windows(
-        ha, ca, [&](const uint8_t* p) { sa.push_back(p); }, snap::NoSets{}, [&](const uint8_t* t) { ta.push_back(t); },
-        [&] { ends.push_back({sa.size(), ta.size()}); });
-    if (!bad && !h->fe_by)
-        bad = snap::walk_windows(
-            hb, cb, [&](const uint8_t* p) { sb.push_back(p); }, snap::NoSets{}, [](const uint8_t*) {},
-            [&] { ends_b.push_back(sb.size()); });
+    // pass 1: kids[0]'s entries and timers, and what finds every entry's element
+    ckpt::FirstElementJoin join;
+    const snap::Err bad = join.open(ba, h->fe_by ? nullptr : &bb);
     if (bad) return h->fail(bad);
-    const int64_t acc_at = snap::state_acc_at(ha), ea = snap::state_entry_bytes(ha);
-    std::vector<int64_t> seqs, by_key, by_start, by_res;
-    for (size_t g = 0; g < ends_b.size(); ++g)
-        if (ends_b[g] != ends[g].first) return h->fail(GW_E_STATE, "first-element snapshot: entries differ");
-    for (size_t i = 0; i < sa.size(); ++i) {
-        if (h->fe_by) {  // (start, end, key, [hash], MIN / MAX)
-            by_start.push_back(snap::state_start(sa[i]));
-            by_key.push_back(snap::state_key(sa[i]));
-            by_res.push_back(snap::get64(sa[i] + acc_at));
-        } else {  // kids[1]: MIN_I64 of the sequence
-            if (memcmp(sa[i], sb[i], (size_t)acc_at) != 0) return h->fail(GW_E_STATE, "first-element snapshot: entries differ");
-            seqs.push_back(snap::get64(sb[i] + acc_at));
-        }
-    }
-    std::vector<int64_t> pays(h->fe_by ? by_key.size() : seqs.size());
-    if (h->fe_by && !by_key.empty()) {
-        const size_t m = by_key.size();
+    std::vector<int64_t> pays(join.a.entries);
+    if (h->fe_by && !join.by_key.empty()) {
+        const size_t m = join.by_key.size();
         DevBuf<int64_t> d;
         HIPCHECK_H(h, d.reserve_discard((int64_t)m * 4));
-        hipError_t e = hipMemcpyAsync(d, by_key.data(), m * 8, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + m, by_start.data(), m * 8, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * m, by_res.data(), m * 8, hipMemcpyHostToDevice, h->stream);
+        hipError_t e = hipMemcpyAsync(d, join.by_key.data(), m * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + m, join.by_start.data(), m * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * m, join.by_res.data(), m * 8, hipMemcpyHostToDevice, h->stream);
         int rc = e == hipSuccess ? by_select(h, (int64_t)m, d, d + m, d + 2 * m, nullptr, d + 3 * m)
                                  : h->fail(GW_E_DEVICE, "minBy / maxBy snapshot: %s", hipGetErrorString(e));
         if (rc == GW_OK && hipMemcpy(pays.data(), d + 3 * m, m * 8, hipMemcpyDeviceToHost) != hipSuccess)
             rc = h->fail(GW_E_DEVICE, "minBy / maxBy snapshot");
         if (rc) return rc;
     }
-    if (!seqs.empty()) {
-        for (int64_t q : seqs)
+    if (const size_t ns = join.seqs.size()) {
+        for (int64_t q : join.seqs)
             if (q < h->fe_log_base || q >= h->fe_seq) return h->fail(GW_E_STATE, "first-element snapshot: payload released");
         DevBuf<int64_t> d;
-        HIPCHECK_H(h, d.reserve_discard((int64_t)seqs.size() * 2));
-        hipError_t e = hipMemcpyAsync(d, seqs.data(), seqs.size() * 8, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = fe_log_gather(h->fe_log, h->fe_log_cap, d, (int64_t)seqs.size(), d + seqs.size(), h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(pays.data(), d + seqs.size(), seqs.size() * 8, hipMemcpyDeviceToHost, h->stream);
+        HIPCHECK_H(h, d.reserve_discard((int64_t)ns * 2));
+        hipError_t e = hipMemcpyAsync(d, join.seqs.data(), ns * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = fe_log_gather(h->fe_log, h->fe_log_cap, d, (int64_t)ns, d + ns, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(pays.data(), d + ns, ns * 8, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) return h->fail(GW_E_DEVICE, "first-element snapshot: %s", hipGetErrorString(e));
     }
     // pass 2: the blob
     snap::Writer w;
-    size_t i = 0, t = 0;
-    for (const auto& end : ends) {
-        w.begin_group();
-        w.count((int32_t)(end.first - i));
-        for (; i < end.first; ++i) {
-            w.bytes(sa[i], ea);
-            snap::put64(w.pay, pays[i]);
-        }
-        w.count(0);
-        w.count((int32_t)(end.second - t));
-        for (; t < end.second; ++t) w.bytes(ta[t], snap::kTimerBytes);
-    }
-    ha.agg = h->cfg.agg;
-    ha.flags |= snap::kFirstElement;
-    return h->finish_blob(w, ha, buf, cap, len);
+    const snap::Header hd = join.write(h->cfg.agg, pays, w);
+    return h->finish_blob(w, hd, buf, cap, len);
 }
 
 static int fe_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
@@ -4480,62 +3881,21 @@ static int fe_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
     // the two operators' blobs (minBy / maxBy: one): kids[0] gets the entries without their
     // payloads, kids[1] (window, key, new sequence); both get the timers
     std::vector<gw_handle*> ops(h->kids.begin(), h->kids.begin() + (h->fe_by ? 1 : 2));
-    std::vector<int64_t> by_cols[3];  // minBy / maxBy: the restored elements' key, window start, field
-    const int64_t acc_at = snap::state_acc_at(hd), ea = snap::state_payload_at(hd);
-    snap::Writer w[2];
-    std::vector<uint8_t> st[2], tm;  // of the current key group
-    std::vector<int64_t> pays;
-    int32_t n = 0;
-    int64_t max_end = INT64_MIN;
-    const int64_t seq0 = h->fe_seq;
-    bad = snap::walk_windows(
-        hd, c,
-        [&](const uint8_t* p) {
-            st[0].insert(st[0].end(), p, p + ea);
-            st[1].insert(st[1].end(), p, p + acc_at);
-            snap::put64(st[1], seq0 + (int64_t)pays.size());  // the restored first element's new sequence
-            pays.push_back(snap::get64(p + ea));
-            max_end = std::max(max_end, snap::state_end(p));
-            n++;
-            if (h->fe_by) {
-                by_cols[0].push_back(snap::state_key(p));
-                by_cols[1].push_back(snap::state_start(p));
-                by_cols[2].push_back(snap::get64(p + acc_at));
-            }
-        },
-        snap::NoSets{"merging window set in a first-element snapshot"},
-        [&](const uint8_t* t) { tm.insert(tm.end(), t, t + snap::kTimerBytes); },
-        [&] {
-            for (int o = 0; o < 2; ++o) {
-                w[o].begin_group();
-                w[o].section(n, st[o]);
-                w[o].section(0, {});
-                w[o].section((int32_t)(tm.size() / snap::kTimerBytes), tm);
-                st[o].clear();
-            }
-            tm.clear();
-            n = 0;
-        });
-    if (bad) return h->fail(bad);
-    std::vector<std::vector<uint8_t>> blobs(ops.size());
-    for (size_t o = 0; o < ops.size(); ++o) {
-        snap::Header kh = hd;
-        kh.flags &= ~snap::kFirstElement;
-        kh.agg = o ? GW_MIN_I64 : h->cfg.agg;
-        blobs[o] = w[o].finish(kh);
-    }
+    ckpt::FirstElementSplit split;
+    if ((bad = split.split(h->cfg.agg, h->fe_seq, hd, c))) return h->fail(bad);
+    const std::vector<std::vector<uint8_t>> blobs(split.blobs, split.blobs + ops.size());
     // checked before the log or any operator changes
     int rc = restore_parts(h, ops, blobs, true);
     if (rc || dry) return rc;
     // the payloads enter the log as one batch released once every restored window is cleaned
-    const int64_t m = (int64_t)pays.size();
+    const int64_t m = (int64_t)split.pays.size();
     if (m) {
         if ((rc = fe_log_reserve(h, m))) return rc;
         DevBuf<int64_t> d;
         HIPCHECK_H(h, d.reserve_discard(m * h->fe_cols));
-        hipError_t e = hipMemcpy(d, pays.data(), (size_t)m * 8, hipMemcpyHostToDevice);
+        hipError_t e = hipMemcpy(d, split.pays.data(), (size_t)m * 8, hipMemcpyHostToDevice);
         for (int c = 1; c < h->fe_cols && e == hipSuccess; ++c)
-            e = hipMemcpy(d + c * m, by_cols[c - 1].data(), (size_t)m * 8, hipMemcpyHostToDevice);
+            e = hipMemcpy(d + c * m, split.by_cols[c - 1].data(), (size_t)m * 8, hipMemcpyHostToDevice);
         for (int c = 0; c < h->fe_cols && e == hipSuccess; ++c)
             e = fe_log_append(h->fe_log + c * h->fe_log_cap, h->fe_log_cap, h->fe_seq, d + c * m, m, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -4543,7 +3903,7 @@ static int fe_restore(gw_handle* h, const void* buf, int64_t len, bool dry) {
         h->fe_seq += m;
         if (h->fe_by) h->fe_restored_end = h->fe_seq;  // restored elements stand for their own window
         // released like a batch whose records reach the latest restored window: maxTs + size - 1 = its end - 1
-        h->fe_batches.push_back({h->fe_seq, 0, max_end - h->cfg.size, true});
+        h->fe_batches.push_back({h->fe_seq, 0, split.max_end - h->cfg.size, true});
     }
     return restore_parts(h, ops, blobs, false);
 }
@@ -4574,142 +3934,26 @@ int gw_restore(gw_handle* h, const void* buf, int64_t len) {
     return rc;
 }
 
-// The blob layout is snap::Header (96 bytes: kg_lo at 60, kg_hi at 64, reserved at 68,
-// entries at 88), kg_offsets[kg_hi - kg_lo + 2], then the entries; an entry is 32 bytes in
-// version 1, `reserved` int64 words in versions 2 and 3 and one byte in version 4.
+// The blob tools (gw_checkpoint.h): host code over any bytes, no handle.
+static int tool_rc(const snap::Err& e) {
+    if (e) g_create_error = e.reason;
+    return e.code;
+}
 int gw_snapshot_slice(const void* blob, int64_t len, int32_t kg, void* out, int64_t cap, int64_t* out_len) {
-    snap::Header hd;
-    snap::Cursor c, part;
-    snap::Err e = out_len ? snap::open(blob, len, 1, snap::kMaxVersion, hd, c) : snap::invalid("snapshot blob too short");
-    if (!e && (kg < hd.kg_lo || kg > hd.kg_hi)) e = snap::invalid("key group outside the blob's key-group range");
-    if (!e) e = snap::group(blob, hd, kg - hd.kg_lo, part);
-    if (e) { g_create_error = e.reason; return e.code; }
-    snap::Writer w;
-    w.begin_group();
-    const int64_t n = part.left();
-    w.bytes(part.take(n), n);
-    hd.kg_lo = hd.kg_hi = kg;
-    if (w.finish(hd, out, cap, out_len)) { g_create_error = "slice buffer too small"; return GW_E_OUTPUT_FULL; }
-    return GW_OK;
+    return tool_rc(ckpt::slice(blob, len, kg, out, cap, out_len));
 }
-
-extern "C++" {
-// Calls f(p, big_endian) for the key field of every entry, merging-set key and timer of a
-// version 2-4 blob; false for a corrupt blob.
-template <class F>
-static bool blob_keys(const uint8_t* b, int64_t len, F&& f) {
-    snap::Header hd;
-    snap::Cursor c;
-    if (snap::open(b, len, 2, snap::kMaxVersion, hd, c)) return false;
-    if (hd.version < 4) {  // fixed entries, key first
-        while (const uint8_t* p = c.take(snap::entry_unit(hd))) f(p, false);
-        return true;
-    }
-    if (hd.assigner == GW_COUNT_TUMBLING) {
-        auto keys = [&](snap::Entries s) {
-            for (int32_t i = 0; i < s.n; ++i) f(s[i] + snap::kCountKeyAt, true);
-        };
-        return !snap::walk_count_windows(hd, c, keys, keys);
-    }
-    return !snap::walk_windows(
-        hd, c, [&](const uint8_t* p) { f(p + snap::kStateKeyAt, true); },
-        [&](const uint8_t* head, int32_t, const uint8_t*) { f(head, true); },
-        [&](const uint8_t* t) { f(t + snap::kTimerKeyAt, true); }, [] {});
-}
-
-static int64_t key_at(const uint8_t* p, bool be) {
-    if (be) return snap::get64(p);
-    int64_t k;
-    memcpy(&k, p, 8);
-    return k;
-}
-
-// Calls f(payload field, window end) for every entry of a first-element blob; false for a
-// corrupt blob or one without payloads.
-template <class F>
-static bool blob_payloads(const uint8_t* b, int64_t len, F&& f) {
-    snap::Header hd;
-    snap::Cursor c;
-    if (snap::open(b, len, 4, 4, hd, c) || !(hd.flags & snap::kFirstElement)) return false;
-    const int64_t at = snap::state_payload_at(hd);
-    return !snap::walk_windows(
-        hd, c, [&](const uint8_t* p) { f(p + at, snap::state_end(p)); }, snap::NoSets{}, [](const uint8_t*) {}, [] {});
-}
-
-}  // extern "C++"
-
 int gw_snapshot_payloads(const void* blob, int64_t len, int64_t* payloads, int64_t cap, int64_t* n,
                          int64_t* max_window_end) {
-    if (!n) return GW_E_INVALID;
-    std::vector<int64_t> ps;
-    int64_t mx = INT64_MIN;
-    if (!blob_payloads((const uint8_t*)blob, len, [&](const uint8_t* p, int64_t e) {
-            ps.push_back(snap::get64(p));
-            mx = std::max(mx, e);
-        })) {
-        g_create_error = "not a first-element snapshot blob";
-        return GW_E_INVALID;
-    }
-    std::sort(ps.begin(), ps.end());
-    ps.erase(std::unique(ps.begin(), ps.end()), ps.end());
-    *n = (int64_t)ps.size();
-    if (max_window_end) *max_window_end = mx;
-    if (!payloads) return GW_OK;
-    if (cap < *n) { g_create_error = "payload buffer too small"; return GW_E_OUTPUT_FULL; }
-    if (!ps.empty()) memcpy(payloads, ps.data(), ps.size() * 8);
-    return GW_OK;
+    return n ? tool_rc(ckpt::payloads(blob, len, payloads, cap, n, max_window_end)) : GW_E_INVALID;
 }
-
 int gw_snapshot_remap_payloads(void* blob, int64_t len, const int64_t* from, const int64_t* to, int64_t n) {
-    if (n < 0 || (n > 0 && (!from || !to))) { g_create_error = "null payload map"; return GW_E_INVALID; }
-    for (int64_t i = 1; i < n; ++i)
-        if (from[i] <= from[i - 1]) { g_create_error = "remap payloads: from[] not ascending"; return GW_E_INVALID; }
-    const bool ok = blob_payloads((const uint8_t*)blob, len, [&](const uint8_t* cp, int64_t) {
-        uint8_t* p = const_cast<uint8_t*>(cp);
-        const int64_t v = snap::get64(p);
-        const int64_t* it = std::lower_bound(from, from + n, v);
-        if (it == from + n || *it != v) return;
-        const int64_t w = to[it - from];
-        for (int i = 0; i < 8; ++i) p[i] = (uint8_t)((uint64_t)w >> (56 - 8 * i));
-    });
-    if (!ok) { g_create_error = "not a first-element snapshot blob"; return GW_E_INVALID; }
-    return GW_OK;
+    return tool_rc(ckpt::remap_payloads(blob, len, from, to, n));
 }
-
 int gw_snapshot_keys(const void* blob, int64_t len, int64_t* keys, int64_t cap, int64_t* n) {
-    if (!n) return GW_E_INVALID;
-    std::vector<int64_t> ks;
-    if (!blob_keys((const uint8_t*)blob, len, [&](const uint8_t* p, bool be) { ks.push_back(key_at(p, be)); })) {
-        g_create_error = "corrupt snapshot blob";
-        return GW_E_INVALID;
-    }
-    std::sort(ks.begin(), ks.end());
-    ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
-    *n = (int64_t)ks.size();
-    if (!keys) return GW_OK;
-    if (cap < *n) { g_create_error = "key buffer too small"; return GW_E_OUTPUT_FULL; }
-    if (!ks.empty()) memcpy(keys, ks.data(), ks.size() * 8);
-    return GW_OK;
+    return n ? tool_rc(ckpt::keys(blob, len, keys, cap, n)) : GW_E_INVALID;
 }
-
 int gw_snapshot_remap_keys(void* blob, int64_t len, const int64_t* from, const int64_t* to, int64_t n) {
-    if (n < 0 || (n > 0 && (!from || !to))) { g_create_error = "null key map"; return GW_E_INVALID; }
-    for (int64_t i = 1; i < n; ++i)
-        if (from[i] <= from[i - 1]) { g_create_error = "remap keys: from[] not ascending"; return GW_E_INVALID; }
-    const bool ok = blob_keys((const uint8_t*)blob, len, [&](const uint8_t* cp, bool be) {
-        uint8_t* p = const_cast<uint8_t*>(cp);
-        const int64_t k = key_at(p, be);
-        const int64_t* it = std::lower_bound(from, from + n, k);
-        if (it == from + n || *it != k) return;
-        const int64_t v = to[it - from];
-        if (be) {
-            for (int i = 0; i < 8; ++i) p[i] = (uint8_t)((uint64_t)v >> (56 - 8 * i));
-        } else {
-            memcpy(p, &v, 8);
-        }
-    });
-    if (!ok) { g_create_error = "corrupt snapshot blob"; return GW_E_INVALID; }
-    return GW_OK;
+    return tool_rc(ckpt::remap_keys(blob, len, from, to, n));
 }
 
 int gw_end_input(gw_handle* h, int64_t* rows_fired) { return gw_advance_watermark(h, INT64_MAX, rows_fired); }
